@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the detection hot path on MI355X (driver contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
         N > 1: one rank per GPU over RCCL.  Started by torch.distributed.run (RANK / WORLD_SIZE in the environment) the process is
         one of the ranks; started plainly it first becomes the parent of N fresh rank processes (single_shot_detection_amd/launch.py,
         the role of bf/training/helpers.py:129-142) and relays rank 0's JSON line -- the parent itself never touches a GPU.
+        A plain run sets up, warms up, times the K training steps and prints the line (images/s, ms_per_step, the head GEMM's roofline
+        from events inside the timed steps).  --full adds every other figure after them: the evaluation / postprocess legs and, at
+        N = 1, deterministic mode, roofline_hbm, per_config, serving, train_graph, step_fn, fast_mode and the CPU baseline.
+        --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs); that step starts from the state
+        before the first step, the same in every run.
 
 A "step" is one pass of the hot path over one batch of synthetic input, inputs resident in HBM:
     pyramid tail: conv-BN-ReLU extras on the last backbone tap (SSD configs)        H2
@@ -18,7 +23,7 @@ A "step" is one pass of the hot path over one batch of synthetic input, inputs r
 Workload: BASELINE.json configs[1] -- ssd_300_vgg16_voc, batch 32 per GPU, 81 classes (the literal of the sample file):
 the two backbone taps (512@37x37, 512@18x18) are N(0,1) NHWC tensors (the backbone itself stays PyTorch-ROCm and is not part
 of the path); the four extras blocks derive the remaining levels.  Weak scaling: per-GPU batch fixed.
-The postprocess (eval) leg is timed separately and reported as nms_boxes_per_sec / postprocess_images_per_sec.
+The postprocess (eval) leg (--full) is timed separately and reported as nms_boxes_per_sec / postprocess_images_per_sec.
 """
 import argparse
 import gc as _pygc
@@ -181,6 +186,40 @@ class HotPath(object):
         self.side_workgroups = int(os.environ.get('SSDK_SIDE_WGS', '0'))
         self.one_launch = not os.environ.get('SSDK_SPLIT_FORWARD')        # forward GEMM: all levels in one grouped launch (only the backward is split)
         self.ordered_backward = bool(os.environ.get('SSDK_ORDERED_BACKWARD'))
+        # --dump-outputs: every step keeps (scores, locs, loss, class_loss, loc_loss) of itself, detached; the last one is what dump_outputs writes
+        self.keep_outputs = False
+        self.last_outputs = None
+        self._initial_state = None
+
+    def _state_tensors(self):
+        """Every tensor a training step changes besides the optimizer's own state: the parameters and buffers of the path's modules."""
+        seen, out = set(), []
+        for m in (self.heads, self.extras, self.tower, self.neck):
+            if m is None:
+                continue
+            for t in list(m.parameters()) + list(m.buffers()):
+                if id(t) not in seen:
+                    seen.add(id(t))
+                    out.append(t)
+        return out
+
+    def save_initial_state(self):
+        """(--dump-outputs) A copy of the path's state before the first step, for restore_initial_state."""
+        with torch.no_grad():
+            self._initial_state = [t.detach().clone() for t in self._state_tensors()]
+
+    def restore_initial_state(self):
+        """(--dump-outputs) Puts parameters and BatchNorm buffers back to their values before the first step and zeroes SGD's momentum
+        buffers (dampening 0: momentum * 0 + g is the first step's update, bit for bit), so that the next step computes from the same state
+        in every run.  Without it the last of many steps does not: the fp32 atomics of the default mode leave rounding-level differences
+        in every step, and the SGD steps carry them on -- from identical states two paths agree to 4e-7 of each array's largest element
+        over 10 steps, and part by 1e-2 in a backbone-tap gradient after 40 (SSD-300, batch 32)."""
+        state = self._state_tensors()
+        with torch.no_grad():
+            torch._foreach_copy_(state, self._initial_state)
+            bufs = [s['momentum_buffer'] for s in self.opt.state.values() if s.get('momentum_buffer') is not None]
+            if bufs:
+                torch._foreach_zero_(bufs)
 
     def pyramid(self):
         sources = list(self.inputs)
@@ -279,6 +318,8 @@ class HotPath(object):
         # runs inside -- BucketedDataParallel's hooks and end-of-backward callback)
         loss.backward(self._one)
         self.opt.step()
+        if self.keep_outputs:
+            self.last_outputs = tuple(t.detach() for t in (scores, locs, loss, class_loss, loc_loss))
         return loss
 
     def resident_ground_truth(self):
@@ -865,6 +906,90 @@ def per_config_legs(device, steps=4, warmup=2):
     return out
 
 
+DUMP_SAMPLE = 1 << 20    # elements per dumped array at most (4 MiB of float32): at most 12 arrays, 48 MiB in all
+DUMP_LIMIT = 64 * 10 ** 6
+
+
+def dump_outputs(hp, directory):
+    """--dump-outputs: what the last timed step gave its caller, as float32 DIR/<name>.npy -- the loss and its two terms (loss, class_loss,
+    loc_loss), the heads' outputs (scores, locs), the gradients of the backbone taps the backbone's backward would receive (input_grad_<i>),
+    and the path's parameters after the SGD step and their gradients (params, param_grads: hp.params in order, each flattened in its logical
+    NCHW order, whatever its memory layout).  An array of more than DUMP_SAMPLE elements is written as a sample: the flattened array at
+    DUMP_SAMPLE distinct flat indices, sorted, drawn by numpy PCG64 seeded with the CRC-32 of its name -- the same in every run of the same
+    arguments.  The step dumped starts from the state before the first step (HotPath.restore_initial_state), so its inputs are the same
+    bits in every run and its outputs agree to rounding (the default mode's fp32 atomics; bit for bit under SSDK_DETERMINISTIC=1)."""
+    import zlib
+    scores, locs, loss, class_loss, loc_loss = hp.last_outputs
+    hp.keep_outputs, hp.last_outputs = False, None
+
+    def grad(t):
+        return t.grad if t.grad is not None else torch.zeros_like(t)
+    arrays = {'loss': loss, 'class_loss': class_loss, 'loc_loss': loc_loss, 'scores': scores, 'locs': locs}
+    for i, x in enumerate(hp.inputs):
+        arrays[f'input_grad_{i}'] = grad(x)
+    arrays['params'] = torch.cat([p.detach().reshape(-1) for p in hp.params])
+    arrays['param_grads'] = torch.cat([grad(p).detach().reshape(-1) for p in hp.params])
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().contiguous().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit(f'bench.py: --dump-outputs would write more than {DUMP_LIMIT} bytes')
+        np.save(os.path.join(directory, f'{name}.npy'), a)
+
+
+def eval_legs(hp, batch, steps, world, barrier):
+    """--full: the evaluation step (heads forward + postprocess; NMS boxes/s = candidates entering NMS per second) and the postprocess alone,
+    on the heads' random-init scores and on a trained-like score distribution."""
+    hp.set_training(False)
+    for _ in range(2):
+        hp.eval_step()
+    quiesce()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        hp.eval_step()
+    barrier()
+    dte = (time.perf_counter() - t0) / steps
+    cand = int(hp.post.last_nms_candidates.sum().item())
+    # postprocess alone
+    scores, locs = hp.forward_heads()
+    scores, locs = scores.detach(), locs.detach()
+    quiesce()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        hp.post.postprocess_padded((scores, locs), hp.anchors)
+    barrier()
+    dtp = (time.perf_counter() - t0) / steps
+    # the same on a "trained-like" score distribution (SURVEY 8d: background logit + 6, about 1 % of the (anchor, class) pairs
+    # pass the 0.01 threshold): the heads' random-init output above is the worst case (every pair passes)
+    tl = scores.clone().view(batch, -1, hp.C)
+    if hp.cfg['score_converter'] == 'SOFTMAX':
+        tl[..., 0] += 6.0
+    else:
+        tl -= 4.6
+    tl = tl.view(batch, -1)
+    hp.post.postprocess_padded((tl, locs), hp.anchors)
+    cand_tl = int(hp.post.last_nms_candidates.sum().item())
+    quiesce()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        hp.post.postprocess_padded((tl, locs), hp.anchors)
+    barrier()
+    dtp_tl = (time.perf_counter() - t0) / steps
+    return {'nms_boxes_per_sec': world * cand / dtp, 'postprocess_images_per_sec': world * batch / dtp,
+            'eval_images_per_sec': world * batch / dte, 'nms_candidates_per_image': cand / batch,
+            'postprocess_trained_like': {'images_per_sec': world * batch / dtp_tl, 'nms_boxes_per_sec': world * cand_tl / dtp_tl,
+                                         'nms_candidates_per_image': cand_tl / batch, 'ms_per_batch': dtp_tl * 1e3}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -872,9 +997,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--config', default='ssd_300_vgg16_voc')
     ap.add_argument('--batch', type=int, default=32, help='per-GPU batch (weak scaling)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra-legs', action='store_true', help='skip roofline_hbm / per_config (they run at N = 1 only)')
-    ap.add_argument('--eval-steps', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, every other figure too: the evaluation / postprocess legs and, at N = 1, the deterministic, '
+                         'roofline_hbm, per_config, serving, train_graph, step_fn and fast_mode legs and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help=f'write what the last timed step computed as DIR/<name>.npy (float32; more than {DUMP_SAMPLE} elements: a fixed sample); '
+                         'that step starts from the state before the first step, the same in every run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-extra-legs', action='store_true', help='--full: skip the legs after the evaluation legs (they run at N = 1 only)')
+    ap.add_argument('--eval-steps', type=int, default=5, help='--full: steps of each evaluation / postprocess leg')
     ap.add_argument('--sync-bn', action='store_true',
                     help='N > 1: synchronise the pyramid tail\'s BatchNorm statistics over the ranks (detection/init.py:85 convert_syncbn_model); '
                          'default is local statistics, the documented local-BN mode of SURVEY.md 8e')
@@ -938,8 +1069,17 @@ def main():
         from single_shot_detection_amd.distributed import convert_sync_batchnorm
         for m in bn_modules:
             convert_sync_batchnorm(m)
+    hp.keep_outputs = bool(args.dump_outputs) and rank == 0
+    # --dump-outputs: the last timed step starts from the state before the first step (every rank: the gradient exchange averages them)
+    last_from_initial = bool(args.dump_outputs)
+    if last_from_initial:
+        hp.save_initial_state()
     for _ in range(args.warmup):
         hp.train_step(world)
+    if last_from_initial:
+        # once outside the timed region too: the first launch of its copy / zero kernels in a process costs ~50 ms (they are loaded then),
+        # which inside the timed region read as +1 ms per step over 50 steps
+        hp.restore_initial_state()
     # the cyclic collector stays out of the timed region (collected just before it instead): a generation-2 pass over the garbage of the
     # warm-up steps is several ms of host time -- more than the host runs ahead of the GPU in a 3.2 ms step
     import gc
@@ -949,7 +1089,9 @@ def main():
         quiesce()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for i in range(args.steps):
+            if last_from_initial and i == args.steps - 1:
+                hp.restore_initial_state()
             hp.train_step(world, timed=True)
         barrier()
         dt = time.perf_counter() - t0
@@ -966,46 +1108,9 @@ def main():
     fwd_ms, fl_img = head_gemm_time(hp)
     flops_step = fl_img * args.batch
     achieved = flops_step / (fwd_ms * 1e-3) / 1e12
-
-    # eval leg: heads forward + postprocess (NMS boxes/s = candidates entering NMS per second)
-    hp.set_training(False)
-    for _ in range(2):
-        hp.eval_step()
-    quiesce()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.eval_steps):
-        hp.eval_step()
-    barrier()
-    dte = (time.perf_counter() - t0) / args.eval_steps
-    cand = int(hp.post.last_nms_candidates.sum().item())
-    # postprocess alone
-    scores, locs = hp.forward_heads()
-    scores, locs = scores.detach(), locs.detach()
-    quiesce()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.eval_steps):
-        hp.post.postprocess_padded((scores, locs), hp.anchors)
-    barrier()
-    dtp = (time.perf_counter() - t0) / args.eval_steps
-    # the same on a "trained-like" score distribution (background logit + 6, about 1 % of the (anchor, class) pairs
-    # pass the 0.01 threshold): the heads' random-init output above is the worst case (every pair passes)
-    tl = scores.clone().view(args.batch, -1, hp.C)
-    if hp.cfg['score_converter'] == 'SOFTMAX':
-        tl[..., 0] += 6.0
-    else:
-        tl -= 4.6
-    tl = tl.view(args.batch, -1)
-    hp.post.postprocess_padded((tl, locs), hp.anchors)
-    cand_tl = int(hp.post.last_nms_candidates.sum().item())
-    quiesce()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.eval_steps):
-        hp.post.postprocess_padded((tl, locs), hp.anchors)
-    barrier()
-    dtp_tl = (time.perf_counter() - t0) / args.eval_steps
+    if hp.keep_outputs:
+        dump_outputs(hp, args.dump_outputs)
+    evals = eval_legs(hp, args.batch, args.eval_steps, world, barrier) if args.full else {}
 
     # a stream-K owner that gave up on a parked partial tile fills the tile with NaN and counts here: never reported as a result
     from single_shot_detection_amd import _lib as _ssdk_lib
@@ -1043,18 +1148,14 @@ def main():
                           # the end of backward() stalled that stream (gloo: the host) -- 0 means the ring was hidden under the tail's backward
                           'buckets': ex_timing, 'ring_ms': [b['ring_ms'] for b in ex_timing], 'exposed_ms': [b['exposed_ms'] for b in ex_timing],
                           'recovered_steps': hp.exchange.recovered_steps}),
-            'nms_boxes_per_sec': world * cand / dtp, 'postprocess_images_per_sec': world * args.batch / dtp,
-            'eval_images_per_sec': world * args.batch / dte, 'nms_candidates_per_image': cand / args.batch,
-            'postprocess_trained_like': {'images_per_sec': world * args.batch / dtp_tl, 'nms_boxes_per_sec': world * cand_tl / dtp_tl,
-                                         'nms_candidates_per_image': cand_tl / args.batch, 'ms_per_batch': dtp_tl * 1e3},
+            **evals,
             'roofline': {'bound': 'mfma', 'kernel': 'igemm_streamk_kernel (forward head GEMMs, all pyramid levels in one grouped stream-K launch of 512 persistent workgroups)',
                          'achieved': achieved, 'peak': PEAK_FP32_MATRIX_TFLOPS, 'unit': 'TFLOP/s',
                          'frac': achieved / PEAK_FP32_MATRIX_TFLOPS,
                          'traffic': measured_traffic(f'{args.config}:b{args.batch}:igemm_fwd_heads'),
                          'algorithmic_gflop_per_step': flops_step / 1e9, 'ms_per_step': fwd_ms},
         }
-        if world == 1 and not args.no_extra_legs:
-            del scores, locs, tl
+        if args.full and world == 1 and not args.no_extra_legs:
             torch.cuda.empty_cache()
             hp.set_training(True)
             out['deterministic'] = deterministic_leg(hp, max(4, args.steps // 2))
@@ -1070,7 +1171,7 @@ def main():
             out['train_graph'] = train_graph_legs(device)
             out['step_fn'] = step_fn_legs(device)
             out['fast_mode'] = fast_mode_legs(device)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(hp)
         print(json.dumps(out), flush=True)
     if world > 1:

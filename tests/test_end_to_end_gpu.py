@@ -489,8 +489,8 @@ def test_bench_n2_path_on_one_gpu_over_gloo():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SSDK_BENCH_ONE_GPU='1', SSDK_BENCH_BACKEND='gloo')
-    out = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-                          '--sync-bn', '--eval-steps', '1'], env=env, cwd=repo, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full',
+                          '--no-cpu-baseline', '--sync-bn', '--eval-steps', '1'], env=env, cwd=repo, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['rccl_ranks'] == 2 and line['collective_backend'] == 'gloo'
@@ -504,6 +504,43 @@ def test_bench_n2_path_on_one_gpu_over_gloo():
     assert len(ex['buckets']) == 2 and ex['buckets'][0]['bytes'] == 36046848 and ex['recovered_steps'] == 0
     assert all(t is not None and t >= 0.0 for t in ex['exposed_ms']) and all(t is not None and t > 0.0 for t in ex['ring_ms'])
     assert all(e <= r + 1e-3 for e, r in zip(ex['exposed_ms'], ex['ring_ms']))
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the line holds the headline fields of exactly K timed steps and
+    none of the --full legs; DIR holds the last step's outputs as float32 .npy files, arrays above bench.DUMP_SAMPLE elements as a sample.
+    Two runs with the same arguments write the same outputs to rounding: the last step starts from the state before the first one (over
+    tens of SGD steps the default mode's rounding differences otherwise grow well beyond rounding)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for r in range(2):
+        dump = tmp_path / f'out{r}'
+        out = subprocess.run([sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1', '--steps', '40', '--warmup', '5', '--batch', '2',
+                              '--dump-outputs', str(dump)], cwd=repo, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        runs.append((json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1]), dump))
+    line, dump = runs[0]
+    assert line['unit'] == 'images/sec' and line['higher_is_better'] is True and line['dtype'] == 'f32' and line['steps'] == 40
+    assert line['value'] > 0 and abs(line['ms_per_step'] - 2 * 1e3 / line['value']) < 1e-6 * line['ms_per_step']
+    assert line['streamk_timeouts'] == 0 and line['roofline']['achieved'] > 0
+    assert not {'cpu_baseline', 'per_config', 'roofline_hbm', 'nms_boxes_per_sec', 'deterministic'} & set(line)
+    names = {'loss', 'class_loss', 'loc_loss', 'scores', 'locs', 'input_grad_0', 'input_grad_1', 'params', 'param_grads'}
+    assert {f[:-4] for f in os.listdir(dump)} == names
+    arrays = {n: np.load(dump / f'{n}.npy') for n in names}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+    assert arrays['loss'].shape == () and arrays['loss'] > 0
+    assert arrays['scores'].shape == (1 << 20,) and arrays['locs'].ndim == 2 and arrays['locs'].shape[0] == 2
+    assert arrays['input_grad_0'].shape == (1 << 20,) and arrays['input_grad_1'].shape == (2, 512, 18, 18)   # 2 x 512 x 37 x 37 is sampled
+    assert np.abs(arrays['input_grad_0']).max() > 0 and np.abs(arrays['input_grad_1']).max() > 0
+    assert arrays['params'].shape == arrays['param_grads'].shape == (1 << 20,) and np.abs(arrays['param_grads']).max() > 0
+    for n, a in arrays.items():
+        b = np.load(runs[1][1] / f'{n}.npy')
+        assert b.shape == a.shape and np.abs(b.astype(np.float64) - a).max() <= 1e-5 * np.abs(a).max(), n
 
 
 def test_hot_path_scopes_its_process_wide_switches():

@@ -4,10 +4,10 @@ O=$R/gpurun_out/r03
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 W=/tmp/r03_work; rm -rf $W; mkdir -p $W
-echo "== bench line"; timeout -k 10 400 python3 $R/bench.py > $O/bench_line.json 2> $O/bench_line.err; echo rc=$?
+echo "== bench line"; timeout -k 10 400 python3 $R/bench.py --full > $O/bench_line.json 2> $O/bench_line.err; echo rc=$?
 stats() {   # tag, bench args...
   tag=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $W/prof_$tag -o p -- python3 $R/bench.py "$@" --no-cpu-baseline --no-extra-legs > $W/prof_$tag.log 2>&1; rc=$?
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $W/prof_$tag -o p -- python3 $R/bench.py --full "$@" --no-cpu-baseline --no-extra-legs > $W/prof_$tag.log 2>&1; rc=$?
   grep "^{" $W/prof_$tag.log | tail -1 > $O/${tag}_bench_line.json
   python3 $R/tools/rocpd_stats.py $W/prof_$tag/p_results.db 45 > $O/${tag}_kernel_stats.md 2>&1
   rm -rf $W/prof_$tag
@@ -21,7 +21,7 @@ stats retina_b32 --config retina_rn50_500_coco --batch 32 --steps 4 --warmup 1
 stats m2det_b16 --config m2det_512_vgg16_coco --batch 16 --steps 4 --warmup 1
 stats mb2_b2 --config ssd_mb2_voc --batch 2 --steps 10 --warmup 2
 echo "== step timeline"
-timeout -k 10 300 rocprofv3 --kernel-trace -d $W/gp -o p -- python3 $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-extra-legs > $W/gp.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace -d $W/gp -o p -- python3 $R/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-extra-legs > $W/gp.log 2>&1
 python3 $R/tools/rocpd_gaps.py $W/gp/p_results.db multi_tensor_apply 5 > $O/step_timeline_ssd300_b32.txt 2>&1
 rm -rf $W/gp
 echo "== fast mode block"
@@ -33,7 +33,7 @@ echo "== pmc passes"
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_BUSY_CYCLES"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $W/pmc_$i -o p -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs > $W/pmc_$i.log 2>&1; echo pmc $i rc=$?
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $W/pmc_$i -o p -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs > $W/pmc_$i.log 2>&1; echo pmc $i rc=$?
 done
 python3 $R/tools/collect_pmc.py $O/pmc.json ssd_300_vgg16_voc:b32 $W/pmc_1 $W/pmc_2 $W/pmc_3 > $O/pmc_collect.log 2>&1
 echo "== postprocess b64 stats"
@@ -51,7 +51,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS S
 done
 python3 $R/tools/collect_pmc.py $O/pmc_post.json ssd_300_vgg16_voc:b64:trained $W/pmcpostt_FETCH_SIZE $W/pmcpostt_WRITE_SIZE $W/pmcpostt_SQ_INSTS_VALU >> $O/pmc_post_collect.log 2>&1
 echo "== 2-rank rehearsal of the self-launching bench (gloo, both ranks on this one GPU)"
-SSDK_BENCH_ONE_GPU=1 SSDK_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err; echo rc=$?
+SSDK_BENCH_ONE_GPU=1 SSDK_BENCH_BACKEND=gloo timeout -k 10 300 python3 $R/bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err; echo rc=$?
 rm -rf $W
 du -sh $O
 echo done

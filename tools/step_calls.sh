@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 CFG=${1:-m2det_512_vgg16_coco}; B=${2:-16}
 cd /tmp && export TMPDIR=/tmp
 W=/tmp/step_calls; rm -rf $W; mkdir -p $W $R/gpurun_out
-timeout -k 10 400 rocprofv3 --kernel-trace -d $W -o p -- python3 $R/bench.py --config $CFG --batch $B --steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs > $W/run.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace -d $W -o p -- python3 $R/bench.py --full --config $CFG --batch $B --steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs > $W/run.log 2>&1
 python3 - $W/p_results.db > $R/gpurun_out/step_calls_$CFG.txt <<'PY'
 import sqlite3, sys, collections
 db = sqlite3.connect(sys.argv[1])
