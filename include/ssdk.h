@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 114
+#define SSDK_VERSION 115
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -45,6 +45,11 @@ extern "C" {
 /* localisation loss kinds */
 #define SSDK_LOC_SMOOTH_L1 0 /* torch.nn.SmoothL1Loss(reduction='sum') on box_coder-encoded targets, multibox_loss.py:81-86 */
 #define SSDK_LOC_GIOU 1      /* GeneralizedIoULoss, losses.py:109-114, on decoded corners (multibox_loss.py:77-79) */
+/* torch.nn.modules.loss re-exported by losses.py:4, reduction='sum', on the encoded targets like SSDK_LOC_SMOOTH_L1 (d = loc - target) */
+#define SSDK_LOC_L1 2        /* torch.nn.L1Loss: |d|, gradient sign(d) with sign(0) = 0 (torch.nn.functional.l1_loss) */
+#define SSDK_LOC_MSE 3       /* torch.nn.MSELoss: d^2, gradient 2d (torch.nn.functional.mse_loss) */
+#define SSDK_LOC_HUBER 4     /* torch.nn.HuberLoss(delta = smooth_l1_beta): |d| < delta ? d^2 / 2 : delta (|d| - delta / 2),
+                                gradient d clamped to [-delta, delta] (torch.nn.functional.huber_loss) */
 
 int ssdk_version(void);
 
@@ -180,6 +185,14 @@ int ssdk_naive_sampler(const float* target_classes, int class_stride, int batch,
  *   (bf/utils/misc_utils.py:22-29).  reduce_mean == 2: out3 holds the plain sums, NOT divided by
  *   max(1, #positives) -- a loss module of bf/modules/losses.py:34-106 on its own (forward(prediction, target) outside
  *   MultiboxLoss).  soft_epsilon: label smoothing of the soft-target losses.
+ *   smooth_l1_beta: beta of SSDK_LOC_SMOOTH_L1 (>= 0; 0 is torch.nn.functional.smooth_l1_loss's L1 case, = SSDK_LOC_L1) and delta of
+ *   SSDK_LOC_HUBER (> 0); unused by the other kinds.
+ *   ce_label_smoothing, class_weight: torch.nn.CrossEntropyLoss(label_smoothing=, weight=) -- SSDK_CLS_CROSS_ENTROPY only (0 / NULL for
+ *   every other kind).  Per sampled row i with label y (ignore_index -1 rows excluded), over the C classes with p = softmax(x_i):
+ *   (1 - ce_label_smoothing) * w_y * (-log p_y) + ce_label_smoothing / C * sum_c w_c * (-log p_c), the reduction='sum' form of
+ *   torch.nn.functional.cross_entropy.  ce_label_smoothing in [0, 1]; class_weight DEV float[C] or NULL (every w_c = 1), read by the
+ *   forward and the backward (keep it alive and at the same address across both -- and across the replays of a captured graph).
+ *   Both fields are appended: a positional initialisation of the older fields leaves them 0 / NULL, i.e. plain cross-entropy.
  */
 typedef struct ssdk_loss_params {
     int cls_kind;  /* SSDK_CLS_* */
@@ -191,7 +204,9 @@ typedef struct ssdk_loss_params {
     float classification_weight;
     float localization_weight;
     float xy_scale, wh_scale, eps; /* BoxCoder */
-    float smooth_l1_beta;
+    float smooth_l1_beta;     /* SmoothL1Loss beta, HuberLoss delta */
+    float ce_label_smoothing; /* CrossEntropyLoss label_smoothing */
+    const float* class_weight; /* CrossEntropyLoss weight, DEV [C] or NULL */
 } ssdk_loss_params;
 
 /*
@@ -200,7 +215,7 @@ typedef struct ssdk_loss_params {
  *   kinds), localisation: loc_kind over the positives.
  *   target DEV [batch, A, 6]: with SSDK_LOC_SMOOTH_L1 it is MUTATED like the reference -- columns 0..3 become the
  *          encoded regression targets (to_centroids + encode_box in place, multibox_loss.py:81-82 / box_coder.py:22-30),
- *          every anchor; with SSDK_LOC_GIOU it is left alone (multibox_loss.py:77-79).
+ *          every anchor (the same for SSDK_LOC_L1 / _MSE / _HUBER); with SSDK_LOC_GIOU it is left alone (multibox_loss.py:77-79).
  *   out3   DEV float[3] = (loss, class_loss, loc_loss), each already divided by max(1, #positives).
  *   lse_valid != 0: the workspace already holds this batch's per-anchor log-sum-exp (left there by
  *          ssdk_hard_negative_mining on the same scores), so the scores are not read again for sampled negatives.

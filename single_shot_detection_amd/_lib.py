@@ -166,7 +166,7 @@ class LossParams(C.Structure):
     _fields_ = [('cls_kind', C.c_int), ('loc_kind', C.c_int), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float),
                 ('reduce_mean', C.c_int), ('soft_epsilon', C.c_float), ('classification_weight', C.c_float),
                 ('localization_weight', C.c_float), ('xy_scale', C.c_float), ('wh_scale', C.c_float), ('eps', C.c_float),
-                ('smooth_l1_beta', C.c_float)]
+                ('smooth_l1_beta', C.c_float), ('ce_label_smoothing', C.c_float), ('class_weight', C.c_void_p)]
 
 
 class ConvDesc(C.Structure):

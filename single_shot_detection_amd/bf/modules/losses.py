@@ -12,12 +12,16 @@ the plain sums instead of MultiboxLoss's division by the positives.  Limits, eac
 'mean' ('none' has no per-row output in the fused kernel), dense targets with at most one non-zero entry per row, SoftmaxFocalLoss's
 ``ignore_index`` mapped onto the kernel's -1.  GeneralizedIoULoss (losses.py:109-114) is 1 - box_utils.generalized_iou on
 csrc/boxes.hip, forward only (no autograd: MultiboxLoss's GIoU term has its backward inside the fused kernel).
+
+torch's own loss classes are re-exported as the reference does (``from torch.nn.modules.loss import *``).  MultiboxLoss puts these of them
+on the fused kernels: CrossEntropyLoss (``label_smoothing``, ``weight``), SmoothL1Loss (``beta``, 0 included), L1Loss, MSELoss and
+HuberLoss (``delta``); any other it refuses with NotImplementedError.
 """
 import ctypes
 
 import torch
 import torch.nn as nn
-from torch.nn.modules.loss import CrossEntropyLoss, SmoothL1Loss  # noqa: F401  (losses.py:4 re-exports torch's)
+from torch.nn.modules.loss import *  # noqa: F401,F403  (losses.py:4 re-exports torch's: a config may name any of them)
 
 SSDK_CLS_SIGMOID_FOCAL = 1
 SSDK_CLS_SOFTMAX_FOCAL = 2

@@ -12,7 +12,8 @@
 //   hnm_select_kernel  one workgroup per image: exact N-th-largest selection by 4x8-bit radix histograms in LDS
 //                      instead of argsort(argsort()); ties at the threshold go to the lower anchor index.
 //   loss_fwd_kernel    one thread per anchor: target encode in place (to_centroids + encode_box, every anchor, as
-//                      the reference mutates it), smooth-L1 over positives, and the classification term for SAMPLED
+//                      the reference mutates it), the box term over positives (smooth-L1, L1, MSE or Huber on the encoded
+//                      target; GIoU on decoded corners), and the classification term for SAMPLED
 //                      rows only (a gather of x[class] when the log-sum-exp is already there; otherwise the wave
 //                      cooperates on each sampled row).  Partial sums per workgroup, fixed-order final reduce.
 //   loss_bwd_kernel    64-row output tiles: zero-fill, fill the sampled rows, one coalesced write.
@@ -322,14 +323,23 @@ __global__ void __launch_bounds__(256) naive_sampler_kernel(const float* __restr
 
 // ---- L1/L2/L3 forward -----------------------------------------------------------------------------------------
 
-// torch smooth_l1: z < beta ? 0.5 z^2 / beta : z - 0.5 beta
-__device__ __forceinline__ float smooth_l1(float a, float b, float beta) {
-    const float z = fabsf(a - b);
-    return z < beta ? 0.5f * z * z / beta : z - 0.5f * beta;
+// Box term of the kinds on encoded targets, per coordinate, prediction a against target b (torch's elementwise forms; beta is
+// SmoothL1's beta or Huber's delta).  A template parameter, so each kind's row loop is its own code (the default SmoothL1 loop as before).
+template <int LK>
+__device__ __forceinline__ float box_loss(float a, float b, float beta) {
+    const float d = a - b, z = fabsf(d);
+    if constexpr (LK == SSDK_LOC_SMOOTH_L1) return z < beta ? 0.5f * z * z / beta : z - 0.5f * beta;   // smooth_l1 (beta > 0)
+    else if constexpr (LK == SSDK_LOC_L1) return z;                                                  // l1_loss
+    else if constexpr (LK == SSDK_LOC_MSE) return d * d;                                             // mse_loss
+    else return z < beta ? 0.5f * z * z : beta * (z - 0.5f * beta);                                  // huber_loss
 }
-__device__ __forceinline__ float smooth_l1_grad(float a, float b, float beta) {
+template <int LK>
+__device__ __forceinline__ float box_loss_grad(float a, float b, float beta) {
     const float d = a - b;
-    return d <= -beta ? -1.0f : (d >= beta ? 1.0f : d / beta);
+    if constexpr (LK == SSDK_LOC_SMOOTH_L1) return d <= -beta ? -1.0f : (d >= beta ? 1.0f : d / beta);
+    else if constexpr (LK == SSDK_LOC_L1) return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);       // sgn(0) = 0
+    else if constexpr (LK == SSDK_LOC_MSE) return 2.0f * d;
+    else return d <= -beta ? -beta : (d >= beta ? beta : d);
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
@@ -356,7 +366,14 @@ struct LossParams {
     float gamma, alpha, xy_scale, wh_scale, eps, beta;
     int loc_kind;
     float epsilon;  // label smoothing of the soft-target losses (losses.py:13-18)
+    float ls;        // CEX kernels: CrossEntropyLoss label_smoothing
+    const float* cw; // CEX kernels: CrossEntropyLoss weight [C] or nullptr
 };
+
+// CrossEntropyLoss weight of class c (1 without weights; 0 for a label outside [0, C), which must not read past the [C] array)
+__device__ __forceinline__ float class_w(const LossParams& p, int c) {
+    return p.cw ? ((unsigned)c < (unsigned)p.C ? p.cw[c] : 0.0f) : 1.0f;
+}
 
 // losses.py:13-18 _soften for a target row with one positive entry of value s at column pos (pos < 0: all-zero row)
 __device__ __forceinline__ float soft_t(int c, int pos, float s, int C, float eps) {
@@ -402,6 +419,9 @@ __device__ __forceinline__ float4 giou_loss_grad(float4 P, float4 T) {
     return d;
 }
 
+// LK: the box-term kind.  CEX: SSDK_CLS_CROSS_ENTROPY with label smoothing and/or class weights -- its own instantiation, so the plain
+// kinds' code (the gather of x[class] off the sampler's log-sum-exp) and register allocation stay what they were.
+template <int LK, bool CEX>
 __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, const float* __restrict__ scores,
                                                                 const float4* __restrict__ locs, const float4* __restrict__ anchors,
                                                                 float* __restrict__ target, const uint8_t* __restrict__ sampled,
@@ -430,7 +450,7 @@ __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, co
             smp = sampled[r] != 0;
             npos += pos;
             const float4 pr = anchors[r % A];
-            if (p.loc_kind == SSDK_LOC_GIOU) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
+            if constexpr (LK == SSDK_LOC_GIOU) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
                 if (pos) {
                     float4 cen;
                     loc_acc += giou_loss(decode_corners(locs[r], pr, p.xy_scale, p.wh_scale, cen), make_float4(t01.x, t01.y, t23.x, t23.y));
@@ -449,18 +469,20 @@ __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, co
             trow[0] = t01; trow[1] = t23;
             if (pos) {  // multibox_loss.py:84-86
                 const float4 l = locs[r];
-                loc_acc += smooth_l1(l.x, t01.x, p.beta) + smooth_l1(l.y, t01.y, p.beta) + smooth_l1(l.z, t23.x, p.beta) +
-                           smooth_l1(l.w, t23.y, p.beta);
+                loc_acc += box_loss<LK>(l.x, t01.x, p.beta) + box_loss<LK>(l.y, t01.y, p.beta) + box_loss<LK>(l.z, t23.x, p.beta) +
+                           box_loss<LK>(l.w, t23.y, p.beta);
             }
             }
         }
-        const bool hard_label = p.cls_kind == SSDK_CLS_CROSS_ENTROPY || p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL;
+        const bool hard_label = CEX || p.cls_kind == SSDK_CLS_CROSS_ENTROPY || p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL;
         const bool want = hard_label ? (smp && cls != -1) : smp;  // CE / softmax focal: ignore_index = -1
         nrows += smp;
-        if (hard_label && p.lse_valid) {
+        if (hard_label && p.lse_valid && (!CEX || p.ls == 0.0f)) {   // (class weights alone: w_y times the same gather)
             if (want) {
                 const float nlogpb = lse[r] - scores[r * p.C + cls];
-                if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY) {
+                if constexpr (CEX) {
+                    cls_acc += class_w(p, cls) * nlogpb;
+                } else if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY) {
                     cls_acc += nlogpb;
                 } else {  // losses.py:56-78
                     float l = __powf(1.0f - __expf(-nlogpb), p.gamma) * nlogpb;
@@ -479,15 +501,27 @@ __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, co
                 const float* x = scores + rs * p.C;
                 float val;
                 if (p.cls_kind != SSDK_CLS_SIGMOID_FOCAL && p.cls_kind != SSDK_CLS_BCE_SOFT) {  // softmax family: needs the row's log-sum-exp
-                    float m = -INFINITY;
-                    for (int c = lane; c < p.C; c += kWave) m = fmaxf(m, x[c]);
-                    m = wave_allreduce(m, OpMaxF());
-                    float s = 0.0f;
-                    for (int c = lane; c < p.C; c += kWave) s += __expf(x[c] - m);
-                    s = wave_allreduce(s, OpAddF());
-                    const float l = m + logf(s);
-                    if (lane == src) lse[rs] = l;
-                    if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY) {
+                    float l;
+                    if (CEX && p.lse_valid) {  // (label smoothing reads the row; the log-sum-exp is the sampler's, as the gather's)
+                        l = lse[rs];
+                    } else {
+                        float m = -INFINITY;
+                        for (int c = lane; c < p.C; c += kWave) m = fmaxf(m, x[c]);
+                        m = wave_allreduce(m, OpMaxF());
+                        float s = 0.0f;
+                        for (int c = lane; c < p.C; c += kWave) s += __expf(x[c] - m);
+                        s = wave_allreduce(s, OpAddF());
+                        l = m + logf(s);
+                        if (lane == src) lse[rs] = l;
+                    }
+                    if constexpr (CEX) {  // torch cross_entropy(weight=w, label_smoothing=ls): nll term + smoothing term
+                        float f = 0.0f;
+                        if (p.ls != 0.0f) {
+                            for (int c = lane; c < p.C; c += kWave) f += class_w(p, c) * (l - x[c]);
+                            f = wave_allreduce(f, OpAddF());
+                        }
+                        val = (1.0f - p.ls) * class_w(p, cs) * (l - x[cs]) + p.ls / (float)p.C * f;
+                    } else if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY) {
                         val = l - x[cs];
                     } else if (p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL) {
                         const float nlogpb = l - x[cs];
@@ -584,6 +618,7 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(const float* __restr
 
 // ---- backward ------------------------------------------------------------------------------------------------
 
+template <int LK, bool CEX>
 __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, int reduce_mean, float cls_w, float loc_w,
                                                                 const float* __restrict__ scores, const float4* __restrict__ locs,
                                                                 const float4* __restrict__ anchors, int A,
@@ -614,7 +649,7 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
             const int cls = (int)t45.x;
             const bool pos = cls != 0 && cls != -1;
             const bool smp = sampled[r] != 0;
-            const bool hard_label = p.cls_kind == SSDK_CLS_CROSS_ENTROPY || p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL;
+            const bool hard_label = p.cls_kind == SSDK_CLS_CROSS_ENTROPY || p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL || CEX;
             const bool want = hard_label ? (smp && cls != -1) : smp;
             s_cls[threadIdx.x] = want ? cls : INT_MIN;
             s_tscore[threadIdx.x] = t45.y;
@@ -622,7 +657,7 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pos) {
                 const float4 l = locs[r];
-                if (p.loc_kind == SSDK_LOC_GIOU) {
+                if constexpr (LK == SSDK_LOC_GIOU) {
                     const float4 pr = anchors[r % A];
                     float4 cen;
                     const float4 P = decode_corners(l, pr, p.xy_scale, p.wh_scale, cen);
@@ -631,8 +666,8 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
                     g = make_float4((d.x + d.z) * pr.z / p.xy_scale * g_loc, (d.y + d.w) * pr.w / p.xy_scale * g_loc,
                                     (d.z - d.x) * 0.5f * cen.z / p.wh_scale * g_loc, (d.w - d.y) * 0.5f * cen.w / p.wh_scale * g_loc);
                 } else {
-                    g = make_float4(smooth_l1_grad(l.x, t01.x, p.beta) * g_loc, smooth_l1_grad(l.y, t01.y, p.beta) * g_loc,
-                                    smooth_l1_grad(l.z, t23.x, p.beta) * g_loc, smooth_l1_grad(l.w, t23.y, p.beta) * g_loc);
+                    g = make_float4(box_loss_grad<LK>(l.x, t01.x, p.beta) * g_loc, box_loss_grad<LK>(l.y, t01.y, p.beta) * g_loc,
+                                    box_loss_grad<LK>(l.z, t23.x, p.beta) * g_loc, box_loss_grad<LK>(l.w, t23.y, p.beta) * g_loc);
                 }
             }
             dlocs[r] = g;
@@ -656,7 +691,20 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
             const long long r = r0 + row;
             const float* x = scores + r * p.C;
             float* o = s_tile + row * p.C;
-            if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY || p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL) {
+            if constexpr (CEX) {
+                // d/dx_c = (1 - ls) w_y (p_c - [c == y]) + ls / C (W p_c - w_c),  W = sum_k w_k
+                const float l = lse[r], a = (1.0f - p.ls) * class_w(p, cls), e = p.ls / (float)p.C;
+                float wsum = (float)p.C;
+                if (p.cw && p.ls != 0.0f) {
+                    wsum = 0.0f;
+                    for (int c = lane; c < p.C; c += kWave) wsum += p.cw[c];
+                    wsum = wave_allreduce(wsum, OpAddF());
+                }
+                for (int c = lane; c < p.C; c += kWave) {
+                    const float pc = __expf(x[c] - l);
+                    o[c] = (a * (pc - (c == cls ? 1.0f : 0.0f)) + e * (wsum * pc - class_w(p, c))) * g_cls;
+                }
+            } else if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY || p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL) {
                 const float l = lse[r];
                 float coef = 1.0f;  // dL/dx_c = coef * (p_c - onehot_c)
                 if (p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL) {
@@ -796,8 +844,12 @@ extern "C" int ssdk_naive_sampler(const float* target_classes, int class_stride,
 static int check_loss_params(const char* fn, const ssdk_loss_params* q) {
     SSDK_REQUIRE(q, SSDK_E_INVALID, "%s: null params", fn);
     SSDK_REQUIRE(q->cls_kind >= SSDK_CLS_CROSS_ENTROPY && q->cls_kind <= SSDK_CLS_BCE_SOFT, SSDK_E_INVALID, "%s: cls_kind=%d", fn, q->cls_kind);
-    SSDK_REQUIRE(q->loc_kind == SSDK_LOC_SMOOTH_L1 || q->loc_kind == SSDK_LOC_GIOU, SSDK_E_INVALID, "%s: loc_kind=%d", fn, q->loc_kind);
-    SSDK_REQUIRE(q->smooth_l1_beta > 0, SSDK_E_INVALID, "%s: beta must be > 0", fn);
+    SSDK_REQUIRE(q->loc_kind >= SSDK_LOC_SMOOTH_L1 && q->loc_kind <= SSDK_LOC_HUBER, SSDK_E_INVALID, "%s: loc_kind=%d", fn, q->loc_kind);
+    SSDK_REQUIRE(q->loc_kind != SSDK_LOC_SMOOTH_L1 || q->smooth_l1_beta >= 0, SSDK_E_INVALID, "%s: SmoothL1 beta must be >= 0", fn);
+    SSDK_REQUIRE(q->loc_kind != SSDK_LOC_HUBER || q->smooth_l1_beta > 0, SSDK_E_INVALID, "%s: Huber delta must be > 0", fn);
+    SSDK_REQUIRE(q->ce_label_smoothing >= 0.0f && q->ce_label_smoothing <= 1.0f, SSDK_E_INVALID, "%s: ce_label_smoothing outside [0, 1]", fn);
+    SSDK_REQUIRE(q->cls_kind == SSDK_CLS_CROSS_ENTROPY || (q->ce_label_smoothing == 0.0f && !q->class_weight), SSDK_E_INVALID,
+                 "%s: ce_label_smoothing / class_weight apply to SSDK_CLS_CROSS_ENTROPY only", fn);
     SSDK_REQUIRE(q->soft_epsilon >= 0.0f && q->soft_epsilon < 1.0f, SSDK_E_INVALID, "%s: epsilon outside [0, 1) (losses.py:15)", fn);
     SSDK_REQUIRE(q->reduce_mean >= 0 && q->reduce_mean <= 2, SSDK_E_INVALID, "%s: reduce_mean=%d (0 sum, 1 mean, 2 sums not divided by the positives)", fn, q->reduce_mean);
     return SSDK_OK;
@@ -808,7 +860,28 @@ static LossParams to_device_params(const ssdk_loss_params* q, int C, int lse_val
     p.cls_kind = q->cls_kind; p.C = C; p.lse_valid = lse_valid;
     p.gamma = q->focal_gamma; p.alpha = q->focal_alpha; p.xy_scale = q->xy_scale; p.wh_scale = q->wh_scale; p.eps = q->eps;
     p.beta = q->smooth_l1_beta; p.loc_kind = q->loc_kind; p.epsilon = q->soft_epsilon;
+    if (p.loc_kind == SSDK_LOC_SMOOTH_L1 && p.beta == 0.0f) p.loc_kind = SSDK_LOC_L1;   // torch smooth_l1_loss: beta == 0 is l1_loss
+    p.ls = q->ce_label_smoothing; p.cw = q->class_weight;   // (check_loss_params: 0 / NULL unless SSDK_CLS_CROSS_ENTROPY)
     return p;
+}
+
+// the loss kernels' instantiation for a box-term kind (LossParams::loc_kind after to_device_params, checked to be 0..4) and for plain /
+// extended cross-entropy (label smoothing or class weights)
+static_assert(SSDK_LOC_SMOOTH_L1 == 0 && SSDK_LOC_GIOU == 1 && SSDK_LOC_L1 == 2 && SSDK_LOC_MSE == 3 && SSDK_LOC_HUBER == 4, "kernel tables");
+using LossFwdFn = decltype(&loss_fwd_kernel<SSDK_LOC_SMOOTH_L1, false>);
+using LossBwdFn = decltype(&loss_bwd_kernel<SSDK_LOC_SMOOTH_L1, false>);
+static bool ce_extended(const LossParams& p) { return p.cls_kind == SSDK_CLS_CROSS_ENTROPY && (p.ls != 0.0f || p.cw); }
+static LossFwdFn fwd_kernel_for(const LossParams& p) {
+    static const LossFwdFn k[2][5] = {
+        {loss_fwd_kernel<0, false>, loss_fwd_kernel<1, false>, loss_fwd_kernel<2, false>, loss_fwd_kernel<3, false>, loss_fwd_kernel<4, false>},
+        {loss_fwd_kernel<0, true>, loss_fwd_kernel<1, true>, loss_fwd_kernel<2, true>, loss_fwd_kernel<3, true>, loss_fwd_kernel<4, true>}};
+    return k[ce_extended(p)][p.loc_kind];
+}
+static LossBwdFn bwd_kernel_for(const LossParams& p) {
+    static const LossBwdFn k[2][5] = {
+        {loss_bwd_kernel<0, false>, loss_bwd_kernel<1, false>, loss_bwd_kernel<2, false>, loss_bwd_kernel<3, false>, loss_bwd_kernel<4, false>},
+        {loss_bwd_kernel<0, true>, loss_bwd_kernel<1, true>, loss_bwd_kernel<2, true>, loss_bwd_kernel<3, true>, loss_bwd_kernel<4, true>}};
+    return k[ce_extended(p)][p.loc_kind];
 }
 
 extern "C" int ssdk_multibox_loss_fwd(const ssdk_loss_params* params, const float* scores, const float* locs, const float* anchors,
@@ -826,7 +899,7 @@ extern "C" int ssdk_multibox_loss_fwd(const ssdk_loss_params* params, const floa
     LossWs w = carve_loss_ws(workspace, (size_t)n_rows, nullptr);
     LossParams p = to_device_params(params, num_classes, lse_valid);
     const int grid = stream_grid(n_rows, kLossThreads);
-    hipLaunchKernelGGL(loss_fwd_kernel, dim3(grid), dim3(kLossThreads), 0, s, p, scores, (const float4*)locs, (const float4*)anchors,
+    hipLaunchKernelGGL(fwd_kernel_for(p), dim3(grid), dim3(kLossThreads), 0, s, p, scores, (const float4*)locs, (const float4*)anchors,
                        target, sampled, n_rows, num_anchors, w.lse, w.partials, w.counts);
     SSDK_CHECK_LAUNCH("loss_fwd_kernel");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, w.partials, grid, w.counts, params->cls_kind, params->reduce_mean,
@@ -857,11 +930,12 @@ extern "C" int ssdk_multibox_loss_bwd_ex(const ssdk_loss_params* params, const f
     const long long n_rows = (long long)batch * num_anchors;
     LossWs w = carve_loss_ws(workspace, (size_t)n_rows, nullptr);
     LossParams p = to_device_params(params, num_classes, 1);
+    const LossBwdFn bwd = bwd_kernel_for(p);
     const size_t lds = (size_t)kTileRows * num_classes * sizeof(float);
     if (lds > 48 * 1024)
-        SSDK_CHECK_HIP(hipFuncSetAttribute((const void*)loss_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SSDK_CHECK_HIP(hipFuncSetAttribute((const void*)bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const bool focal = params->cls_kind == SSDK_CLS_SIGMOID_FOCAL || params->cls_kind == SSDK_CLS_SOFTMAX_FOCAL;
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3((unsigned)std::min<long long>((n_rows + kTileRows - 1) / kTileRows, 1 << 20)), dim3(kLossThreads), lds, s, p, focal ? params->reduce_mean : 0,
+    hipLaunchKernelGGL(bwd, dim3((unsigned)std::min<long long>((n_rows + kTileRows - 1) / kTileRows, 1 << 20)), dim3(kLossThreads), lds, s, p, focal ? params->reduce_mean : 0,
                        params->classification_weight, params->localization_weight, scores, (const float4*)locs, (const float4*)anchors,
                        num_anchors, target, sampled, grad_out, n_rows, w.lse, w.state, dscores, (float4*)dlocs, row_mask, grad_single ? 1 : 0);
     SSDK_CHECK_LAUNCH("loss_bwd_kernel");

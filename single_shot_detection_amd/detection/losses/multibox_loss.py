@@ -18,6 +18,9 @@ SSDK_CLS_CE_SOFT = 3
 SSDK_CLS_BCE_SOFT = 4
 SSDK_LOC_SMOOTH_L1 = 0
 SSDK_LOC_GIOU = 1
+SSDK_LOC_L1 = 2
+SSDK_LOC_MSE = 3
+SSDK_LOC_HUBER = 4
 
 
 _NO_ROW_HINT = bool(__import__('os').environ.get('SSDK_NO_ROW_HINT'))   # (measurement knob: the heads scan dscores as before round 4)
@@ -61,7 +64,7 @@ class _MultiboxLossFn(torch.autograd.Function):
         else:  # any user sampler with the reference's signature (multibox_loss.py:58)
             mask = module.sampler(scores.view(B, A, C), cls_col.long()).to(torch.uint8).contiguous()
         out3 = torch.empty((3,), dtype=torch.float32, device=dev)
-        params = module.loss_params()
+        params = module.loss_params(dev, C)
         _lib.check(lib.ssdk_multibox_loss_fwd(ctypes.byref(params), _lib.ptr(scores), _lib.ptr(locs), _lib.ptr(anchors),
                                               _lib.ptr(target), _lib.ptr(mask), B, A, C, lse_valid, _lib.ptr(out3), _lib.ptr(ws),
                                               ws.numel(), _lib.current_stream()), 'ssdk_multibox_loss_fwd')
@@ -92,7 +95,7 @@ class _MultiboxLossFn(torch.autograd.Function):
                                     gt + (zero if g_loc is None else g_loc.float().reshape(()))]).contiguous()
         dscores = torch.empty_like(scores)
         dlocs = torch.empty_like(locs)
-        params = module.loss_params()
+        params = module.loss_params(scores.device, C)
         # under hard-negative mining a few % of the anchors carry a gradient: the kernel also writes which (row_mask), and the heads'
         # backward of this pass -- if it receives these very tensors -- reads only those rows instead of scanning all of dscores
         row_mask = torch.empty((B, A), dtype=torch.uint8, device=scores.device) if ctx.sparse_rows and not _NO_ROW_HINT else None
@@ -132,11 +135,18 @@ class MultiboxLoss(nn.Module):
 
         cl = self.classification_loss
         self.focal_gamma, self.focal_alpha, self.focal_reduce_mean, self.soft_epsilon = 2.0, 0.25, 0, 0.0
+        self.ce_label_smoothing, self.class_weight = 0.0, None
         if isinstance(cl, losses.CrossEntropyLoss):
-            if cl.reduction != 'sum' or cl.ignore_index != IGNORE_CLASS or cl.weight is not None or \
-                    getattr(cl, 'label_smoothing', 0.0) != 0.0:
-                raise NotImplementedError('CrossEntropyLoss: only reduction=sum, ignore_index=-1, no weights/smoothing')
+            if cl.reduction != 'sum' or cl.ignore_index != IGNORE_CLASS:
+                raise NotImplementedError('CrossEntropyLoss: only reduction=sum, ignore_index=-1')
             self.cls_kind = SSDK_CLS_CROSS_ENTROPY
+            self.ce_label_smoothing = float(cl.label_smoothing)
+            if not 0.0 <= self.ce_label_smoothing <= 1.0:
+                raise ValueError(f'CrossEntropyLoss: label_smoothing={self.ce_label_smoothing} outside [0, 1]')
+            if cl.weight is not None:
+                if cl.weight.dim() != 1:
+                    raise ValueError('CrossEntropyLoss: weight must be a 1-D tensor of one value per class')
+                self.class_weight = cl.weight.detach()
         elif isinstance(cl, losses.SigmoidFocalLoss):
             if cl.reduction not in ('mean', 'sum'):
                 raise NotImplementedError("SigmoidFocalLoss: reduction must be 'mean' or 'sum'")
@@ -158,21 +168,48 @@ class MultiboxLoss(nn.Module):
         else:
             raise NotImplementedError(f'classification loss {type(cl).__name__} is not on the GPU path')
         ll = self.localization_loss
-        self.smooth_l1_beta = 1.0
+        self.smooth_l1_beta = 1.0   # (SmoothL1Loss beta; HuberLoss delta)
         if isinstance(ll, losses.SmoothL1Loss) and ll.reduction == 'sum':
             self.loc_kind = SSDK_LOC_SMOOTH_L1
-            self.smooth_l1_beta = float(getattr(ll, 'beta', 1.0))
+            self.smooth_l1_beta = float(getattr(ll, 'beta', 1.0))   # (0: torch's L1 case, taken by the kernel as such)
+            if self.smooth_l1_beta < 0:
+                raise ValueError(f'SmoothL1Loss: beta={self.smooth_l1_beta} must be >= 0')
         elif isinstance(ll, losses.GeneralizedIoULoss) and ll.reduction == 'sum':
             self.loc_kind = SSDK_LOC_GIOU
+        elif isinstance(ll, losses.L1Loss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_L1
+        elif isinstance(ll, losses.MSELoss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_MSE
+        elif isinstance(ll, losses.HuberLoss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_HUBER
+            self.smooth_l1_beta = float(ll.delta)
+            if self.smooth_l1_beta <= 0:
+                raise ValueError(f'HuberLoss: delta={self.smooth_l1_beta} must be > 0')
         else:
             raise NotImplementedError(f'localization loss {type(ll).__name__}(reduction={ll.reduction}) is not on the GPU path')
+        self._class_weight_dev = {}   # device -> the fp32 [C] copy of class_weight the kernels read (one per device, kept: graph replays)
         self.last_sampled_mask = None
 
-    def loss_params(self):
+    def class_weight_on(self, device, num_classes):
+        """CrossEntropyLoss ``weight`` as a contiguous fp32 [C] tensor on ``device`` (None without weights).  Made on the first call for a
+        device and kept by this object, so every later forward / backward -- and a captured graph's replays -- read the same address."""
+        if self.class_weight is None:
+            return None
+        if self.class_weight.numel() != num_classes:
+            raise ValueError(f'CrossEntropyLoss: weight has {self.class_weight.numel()} values for {num_classes} classes')
+        w = self._class_weight_dev.get(device)
+        if w is None:
+            w = self.class_weight.to(device=device, dtype=torch.float32).contiguous()
+            self._class_weight_dev[device] = w
+        return w
+
+    def loss_params(self, device=None, num_classes=None):
+        """ssdk_loss_params of this loss; ``device`` / ``num_classes`` place the class weights (needed only with a ``weight``)."""
+        w = self.class_weight_on(device, num_classes) if self.class_weight is not None else None
         return _lib.LossParams(self.cls_kind, self.loc_kind, self.focal_gamma, self.focal_alpha, self.focal_reduce_mean,
                                self.soft_epsilon, float(self.classification_weight), float(self.localization_weight),
                                float(self.box_coder.xy_scale), float(self.box_coder.wh_scale), float(self.box_coder.eps),
-                               self.smooth_l1_beta)
+                               self.smooth_l1_beta, self.ce_label_smoothing, None if w is None else w.data_ptr())
 
     def forward(self, pred, anchors, target):
         """
