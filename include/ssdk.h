@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 115
+#define SSDK_VERSION 116
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -577,6 +577,33 @@ int ssdk_depthwise_conv2d_fwd(const float* x, const float* w, const float* bias,
                               int stride, int pad, float* y, void* stream);
 int ssdk_depthwise_conv2d_bwd(const float* x, const float* w, const float* dy, int batch, int hin, int win, int channels, int ksize,
                               int stride, int pad, float* dx, float* dw, float* db, int accumulate, void* stream);
+
+/* ---- depthwise feature pyramid (Tiny-DSOD D-FPN, bf/modules/features.py:123-212) ------------------------------------------------
+ * NHWC fp32, channels % 4 == 0, 16-byte aligned maps.  Arguments are checked on the host before any launch (negative status).
+ *
+ * features.py:188-195  down[0](F.pad(f, [0, pad_right, 0, pad_bottom])) starts with nn.MaxPool2d(2): the 2 x 2 / stride 2 max-pool of the
+ * map padded with pad_bottom (0 or 1) zero rows and pad_right zero columns; y [batch, (h + pad_bottom) / 2, (w + pad_right) / 2, channels].
+ * The pad is a real 0.0 that takes part in the max.  torch's CPU rule: window order (0,0), (0,1), (1,0), (1,1), the first maximum wins a
+ * tie, NaN wins.  A map without a single window (h + pad_bottom < 2 or w + pad_right < 2) is refused.
+ * bwd: dx [batch, h, w, channels] is OVERWRITTEN -- dy at each window's maximum (recomputed from x), 0 elsewhere and where the maximum is
+ * in the pad (F.pad drops that gradient).  Gather form: no atomics, deterministic. */
+int ssdk_maxpool2x2_fwd(const float* x, int batch, int h, int w, int channels, int pad_bottom, int pad_right, float* y, void* stream);
+int ssdk_maxpool2x2_bwd(const float* x, const float* dy, int batch, int h, int w, int channels, int pad_bottom, int pad_right, float* dx,
+                        void* stream);
+/* features.py:198  torch.cat(pieces, dim=1): n_pieces (1..8, host array of device pointers) maps of `rows` pixels with piece_channels[k]
+ * (host array, each % 4 == 0) channels -> out [rows, sum of the channels]; bwd: the split, each dpieces[k] written as its own map. */
+int ssdk_concat_channels_fwd(const float* const* pieces, const int* piece_channels, int n_pieces, long long rows, float* out, void* stream);
+int ssdk_concat_channels_bwd(const float* dout, const int* piece_channels, int n_pieces, long long rows, float* const* dpieces, void* stream);
+/* features.py:203-205  up_conv[i](F.interpolate(coarse, size=(hf, wf), mode='nearest')), the convolution half of Conv2dBn(C, C, 3,
+ * padding=1, groups=C): a 3 x 3 depthwise convolution, pad 1, stride 1, of the nearest-upsampled map, reading `coarse` [batch, hc, wc,
+ * channels] through torch's index map (that of ssdk_upsample_nearest_add) -- the upsampled map is never built.  w [channels][9], optional
+ * bias; y [batch, hf, wf, channels].
+ * bwd: dcoarse (may be NULL) is the gather over the fine pixels of each coarse pixel (no atomics); dw [channels][9] and db (may be NULL)
+ * are OVERWRITTEN, reduced as ssdk_depthwise_conv2d_bwd's (in a fixed order in deterministic mode). */
+int ssdk_depthwise_upsample_conv2d_fwd(const float* coarse, const float* w, const float* bias, int batch, int hc, int wc, int hf, int wf,
+                                       int channels, float* y, void* stream);
+int ssdk_depthwise_upsample_conv2d_bwd(const float* coarse, const float* w, const float* dy, int batch, int hc, int wc, int hf, int wf,
+                                       int channels, float* dcoarse, float* dw, float* db, void* stream);
 
 /* ---- device-resident input side ---------------------------------------------------------------------
  * bf/core/batch_container.py:25-45  BatchContainer.mixup_ with the random draws (lam ~ Beta(alpha, alpha), index = randperm(B),

@@ -122,6 +122,111 @@ def _upsample_add(fine, coarse, mode):
     return fine + F.interpolate(coarse, size=fine.shape[2:], mode=mode)
 
 
+class DepthwiseFeaturePyramid(Features):
+    """Tiny-DSOD D-FPN neck (arXiv:1807.11013) -- restatement of bf/modules/features.py:123-212.
+
+    Laterals are 1 x 1 convolutions with bias; each extra level concatenates a max-pool -> 1 x 1 Conv2dBn path with a stride-2
+    DepthwiseConv2dBn path (C/2 channels each); the up path adds ``up_conv[i](nearest(coarser level))`` -- a depthwise 3 x 3 Conv2dBn -- to
+    every finer level.  On libssdk: laterals on ``ops.conv2d``, the zero-padded max-pool on ``ops.maxpool2x2``, the concatenation on
+    ``ops.concat_channels``, the up step's convolution on ``ops.depthwise_upsample_conv2d`` (the upsampled map is never built), its
+    BatchNorm on the project's norm path, the residual on ``ssdk_upsample_nearest_add`` at equal sizes.  Module names follow the reference
+    so checkpoints map 1:1.  An activation other than ReLU / None, a mode other than 'nearest' or a channel count that is not a multiple of 8
+    runs the reference's graph on the stock modules, said once per reason."""
+
+    def __init__(self, base, out_layers, pyramid_layers, pyramid_channels, interpolation_mode='nearest',
+                 activation={'name': 'ReLU', 'args': {'inplace': True}}, initializer={'name': 'xavier_normal_'}, **kwargs):
+        # (features.py:133 forwards **kwargs only: `initializer` never reaches Features, init_layer is always xavier_normal_)
+        super(DepthwiseFeaturePyramid, self).__init__(base, out_layers, **kwargs)
+        self.pyramid_layers = pyramid_layers
+        self.pyramid_channels = pyramid_channels
+        self.interpolation_mode = interpolation_mode
+        self.pyramid_lateral = nn.ModuleList()
+        self.downsample = nn.ModuleList()
+        self.up_conv = nn.ModuleList()
+        self.num_outputs = pyramid_layers
+        base_out_channels = super(DepthwiseFeaturePyramid, self).get_out_channels()
+        for in_channels in base_out_channels:
+            self.pyramid_lateral.append(nn.Conv2d(in_channels, pyramid_channels, kernel_size=1))
+        for _ in range(pyramid_layers - len(out_layers)):
+            paths = nn.ModuleList()
+            paths.append(nn.Sequential(nn.MaxPool2d(kernel_size=2),
+                                       conv.Conv2dBn(pyramid_channels, pyramid_channels // 2, kernel_size=1, activation_params=activation)))
+            paths.append(conv.DepthwiseConv2dBn(pyramid_channels, pyramid_channels // 2, kernel_size=3, stride=2, padding=1,
+                                                activation_params=activation))
+            self.downsample.append(paths)
+        for _ in range(pyramid_layers - 1):
+            self.up_conv.append(conv.Conv2dBn(pyramid_channels, pyramid_channels, kernel_size=3, padding=1, groups=pyramid_channels,
+                                              activation_params=activation))
+        self.pyramid_lateral.apply(self.init_layer)
+        self.downsample.apply(self.init_layer)
+        self.up_conv.apply(self.init_layer)
+        for m in self.modules():   # init rewrote the weights: restore the channels_last memory the GEMM kernels read
+            if isinstance(m, conv.Conv2dBn):
+                m.conv.weight.data = m.conv.weight.data.contiguous(memory_format=torch.channels_last)
+        self._stock_reason = self._why_stock(activation)
+
+    def _why_stock(self, activation):
+        if activation is not None and activation['name'] != 'ReLU':
+            return f"activation {activation['name']}"
+        if self.interpolation_mode != 'nearest':
+            return f'interpolation_mode={self.interpolation_mode!r}'
+        if self.pyramid_channels % 8:
+            return f'pyramid_channels={self.pyramid_channels} (the kernels take multiples of 8: two halves of 4-channel quads)'
+        return None
+
+    def forward(self, x):
+        sources, _ = super(DepthwiseFeaturePyramid, self).forward(x)
+        if self._stock_reason is not None:
+            conv._warn_stock('DepthwiseFeaturePyramid', self._stock_reason)
+            return self._forward_stock(sources)
+        return self.neck(sources)
+
+    def neck(self, sources):
+        """Everything behind the backbone taps (features.py:180-209) on libssdk."""
+        if self.training:   # one re-layout launch for the backward-data GEMMs of the laterals and the downsample paths' 1 x 1 convolutions
+            ops.prepare_weight_transposes(nn.ModuleList([self.pyramid_lateral, self.downsample]))
+        features = [ops.conv2d(s, lat.weight, lat.bias) for s, lat in zip(sources, self.pyramid_lateral)]   # :180-184
+        for down in self.downsample:                                                                       # :186-198
+            f = features[-1]
+            h, w = f.shape[2], f.shape[3]
+            if h < 2 or w < 2:
+                raise ValueError(f'DepthwiseFeaturePyramid: level {len(features) - 1} is {h} x {w}; the next level\'s 2 x 2 max-pool needs '
+                                 'at least 2 rows and 2 columns (the reference\'s max_pool2d fails on it too)')
+            first = down[0][1](ops.maxpool2x2(f, int(h > 2), int(w > 2)))
+            second = down[1](f)
+            features.append(ops.concat_channels([first, second]))
+        output = [features[-1]]
+        for i in reversed(range(len(features) - 1)):                                                       # :200-205
+            uc = self.up_conv[i]
+            y = ops.depthwise_upsample_conv2d(output[-1], uc.conv.weight, uc.conv.bias, features[i].shape[2:])
+            y = conv._norm_act(y, uc.bn, uc._modules.get('activation'))
+            output.append(ops.upsample_add(y, features[i]))   # (equal sizes: the residual add, after the activation)
+        output = list(reversed(output))
+        return output, output[-1]
+
+    def _forward_stock(self, sources):
+        """features.py:180-209 as the reference runs it (stock modules; each block still picks its own path)."""
+        features = [lateral(source) for source, lateral in zip(sources, self.pyramid_lateral)]
+        for down in self.downsample:
+            padding = [0, 0, 0, 0]
+            if features[-1].shape[3] > 2:
+                padding[0:2] = [0, 1]
+            if features[-1].shape[2] > 2:
+                padding[2:4] = [0, 1]
+            first = down[0](F.pad(features[-1], padding))
+            second = down[1](features[-1])
+            features.append(torch.cat([first, second], dim=1))
+        output = [features[-1]]
+        for i in reversed(range(0, len(features) - 1)):
+            up = F.interpolate(output[-1], size=features[i].size()[2:], mode=self.interpolation_mode)
+            output.append(self.up_conv[i](up) + features[i])
+        output = list(reversed(output))
+        return output, output[-1]
+
+    def get_out_channels(self):
+        return [self.pyramid_channels] * self.pyramid_layers
+
+
 def update_existing(dict1, dict2):
     """bf/utils/misc_utils.py:31-34: fill in keys that are missing."""
     for k, v in dict2.items():

@@ -1017,3 +1017,359 @@ extern "C" int ssdk_depthwise_conv2d_bwd(const float* x, const float* w, const f
     }
     return SSDK_OK;
 }
+
+// ---- depthwise feature pyramid (Tiny-DSOD D-FPN, bf/modules/features.py:123-212) -------------------------------------------
+// The three ops of the D-FPN neck that the kernels above do not cover: the zero-padded 2x2 max-pool of the downsample path's first
+// branch (:188-195), the channel concatenation of the two branches (:198), and the up path's depthwise 3x3 convolution of a
+// nearest-upsampled map (:203-205; the upsampled map is never built).  NHWC fp32, a thread owns 4 consecutive channels (float4).
+// Every reduction below except the weight gradient is a gather (no atomics); the weight gradient follows dw_wgrad_kernel.
+namespace ssdk {
+
+// The 2x2 window (yo, xo) of the zero-padded map: rows 2yo, 2yo+1 and columns 2xo, 2xo+1; a row >= H or a column >= W is the pad
+// and reads 0.0 (features.py:188-192 pads with F.pad's zeros, a real value that takes part in the max).
+__device__ __forceinline__ void mp_window(const float4* __restrict__ x, int b, int yo, int xo, int H, int W, int C4, int c4, float4 (&v)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int y = 2 * yo + (k >> 1), xx = 2 * xo + (k & 1);
+        v[k] = (y < H && xx < W) ? x[(((long long)b * H + y) * W + xx) * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// torch's CPU max-pool rule over the window order (0,0), (0,1), (1,0), (1,1): `val > max || isnan(val)` -- the first maximum wins a tie,
+// a NaN wins.  Returns the window position of the maximum.
+__device__ __forceinline__ int mp_arg(float a0, float a1, float a2, float a3, float& m) {
+    int k = 0;
+    m = a0;
+    if (a1 > m || a1 != a1) { m = a1; k = 1; }
+    if (a2 > m || a2 != a2) { m = a2; k = 2; }
+    if (a3 > m || a3 != a3) { m = a3; k = 3; }
+    return k;
+}
+
+__global__ void __launch_bounds__(256) maxpool2x2_kernel(const float4* __restrict__ x, int B, int H, int W, int C4, int Ho, int Wo,
+                                                         float4* __restrict__ y) {
+    const long long total = (long long)B * Ho * Wo * C4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % C4);
+        long long p = i / C4;
+        const int xo = (int)(p % Wo); p /= Wo;
+        const int yo = (int)(p % Ho);
+        const int b = (int)(p / Ho);
+        float4 v[4], m;
+        mp_window(x, b, yo, xo, H, W, C4, c4, v);
+        mp_arg(v[0].x, v[1].x, v[2].x, v[3].x, m.x);
+        mp_arg(v[0].y, v[1].y, v[2].y, v[3].y, m.y);
+        mp_arg(v[0].z, v[1].z, v[2].z, v[3].z, m.z);
+        mp_arg(v[0].w, v[1].w, v[2].w, v[3].w, m.w);
+        y[i] = m;
+    }
+}
+
+// Gather form of the backward: the windows do not overlap, so the thread of window (yo, xo) writes every input cell of it -- dy where the
+// cell is the window's maximum (recomputed from x, no stored indices), 0 elsewhere; a maximum that sits in the pad drops its gradient.
+// The last window row / column also writes the input rows / columns no window covers (odd H or W without a pad): zeros.
+__global__ void __launch_bounds__(256) maxpool2x2_bwd_kernel(const float4* __restrict__ x, const float4* __restrict__ dy, int B, int H, int W,
+                                                             int C4, int Ho, int Wo, float4* __restrict__ dx) {
+    const long long total = (long long)B * Ho * Wo * C4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % C4);
+        long long p = i / C4;
+        const int xo = (int)(p % Wo); p /= Wo;
+        const int yo = (int)(p % Ho);
+        const int b = (int)(p / Ho);
+        float4 v[4];
+        float m;
+        mp_window(x, b, yo, xo, H, W, C4, c4, v);
+        const int kx = mp_arg(v[0].x, v[1].x, v[2].x, v[3].x, m), ky = mp_arg(v[0].y, v[1].y, v[2].y, v[3].y, m);
+        const int kz = mp_arg(v[0].z, v[1].z, v[2].z, v[3].z, m), kw = mp_arg(v[0].w, v[1].w, v[2].w, v[3].w, m);
+        const float4 g = dy[i];
+        const int y1 = yo == Ho - 1 ? H : 2 * yo + 2, x1 = xo == Wo - 1 ? W : 2 * xo + 2;
+        for (int yy = 2 * yo; yy < y1; ++yy) {
+            for (int xx = 2 * xo; xx < x1; ++xx) {
+                const int k = (yy - 2 * yo < 2 && xx - 2 * xo < 2) ? (yy - 2 * yo) * 2 + (xx - 2 * xo) : -1;
+                dx[(((long long)b * H + yy) * W + xx) * C4 + c4] = make_float4(k == kx ? g.x : 0.f, k == ky ? g.y : 0.f, k == kz ? g.z : 0.f,
+                                                                                k == kw ? g.w : 0.f);
+            }
+        }
+    }
+}
+
+// torch.cat(pieces, dim=1) of NHWC maps with `rows` pixels each, and its split (the gradient of every piece as its own contiguous map).
+struct CatPieces {
+    float4* p[kMaxPieces];
+    int c4[kMaxPieces];         // float4 columns of piece k
+    int off4[kMaxPieces + 1];   // its first column in the concatenated row; off4[n] = the row length
+    int n;
+};
+__device__ __forceinline__ int cat_piece(const CatPieces& ps, int c) {
+    int k = 0;
+    while (k + 1 < ps.n && c >= ps.off4[k + 1]) ++k;
+    return k;
+}
+__global__ void __launch_bounds__(256) concat_kernel(CatPieces ps, long long rows, float4* __restrict__ out) {
+    const int C4 = ps.off4[ps.n];
+    const long long total = rows * C4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / C4;
+        const int c = (int)(i - row * C4);
+        const int k = cat_piece(ps, c);
+        out[i] = ps.p[k][row * ps.c4[k] + (c - ps.off4[k])];
+    }
+}
+__global__ void __launch_bounds__(256) split_kernel(const float4* __restrict__ dout, long long rows, CatPieces ds) {
+    const int C4 = ds.off4[ds.n];
+    const long long total = rows * C4;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / C4;
+        const int c = (int)(i - row * C4);
+        const int k = cat_piece(ds, c);
+        ds.p[k][row * ds.c4[k] + (c - ds.off4[k])] = dout[i];
+    }
+}
+
+// y[b,yo,xo,c] = bias[c] + sum_tap w[c][tap] * up[b, yo - 1 + ky, xo - 1 + kx, c],  up = nearest(coarse -> Hf x Wf), zero outside the map:
+// the 3 x 3 depthwise convolution (pad 1, stride 1) of features.py:203-205 reads the coarse map through nearest_src, the index map of
+// ssdk_upsample_nearest_add (torch's), so the padding is that of the fine resolution.
+constexpr int kDwUpTaps = 9;
+__global__ void __launch_bounds__(256) dwup_fwd_kernel(const float4* __restrict__ coarse, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       int B, int Hc, int Wc, int Hf, int Wf, int C4, float4* __restrict__ y) {
+    const long long total = (long long)B * Hf * Wf * C4;
+    const float sh = (float)Hc / (float)Hf, sw = (float)Wc / (float)Wf;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % C4);
+        long long p = i / C4;
+        const int xo = (int)(p % Wf); p /= Wf;
+        const int yo = (int)(p % Hf);
+        const int b = (int)(p / Hf);
+        float4 acc = bias ? *reinterpret_cast<const float4*>(bias + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* wc = w + (long long)c4 * 4 * kDwUpTaps;
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = yo - 1 + ky;
+            if (iy < 0 || iy >= Hf) continue;
+            const long long rowc = ((long long)b * Hc + nearest_src(iy, sh, Hc)) * Wc;
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = xo - 1 + kx;
+                if (ix < 0 || ix >= Wf) continue;
+                const float4 v = coarse[(rowc + nearest_src(ix, sw, Wc)) * C4 + c4];
+                const int t = ky * 3 + kx;
+                acc.x = fmaf(wc[t], v.x, acc.x);
+                acc.y = fmaf(wc[kDwUpTaps + t], v.y, acc.y);
+                acc.z = fmaf(wc[2 * kDwUpTaps + t], v.z, acc.z);
+                acc.w = fmaf(wc[3 * kDwUpTaps + t], v.w, acc.w);
+            }
+        }
+        y[i] = acc;
+    }
+}
+
+// dcoarse[b,yc,xc,c] = sum over the fine pixels (y, x) whose nearest source is (yc, xc) of sum_tap w[c][tap] * dy[b, y + 1 - ky, x + 1 - kx, c]
+// (gather form, the candidate rows / columns of upsample_add_bwd_kernel: deterministic)
+__global__ void __launch_bounds__(256) dwup_dgrad_kernel(const float4* __restrict__ dy, const float* __restrict__ w, int B, int Hc, int Wc, int Hf,
+                                                         int Wf, int C4, float4* __restrict__ dcoarse) {
+    const long long total = (long long)B * Hc * Wc * C4;
+    const float sh = (float)Hc / (float)Hf, sw = (float)Wc / (float)Wf;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % C4);
+        long long p = i / C4;
+        const int xc = (int)(p % Wc); p /= Wc;
+        const int yc = (int)(p % Hc);
+        const int b = (int)(p / Hc);
+        const int y0 = max(0, (int)floorf((float)yc / sh) - 2), y1 = min(Hf - 1, (int)ceilf((float)(yc + 1) / sh) + 2);
+        const int x0 = max(0, (int)floorf((float)xc / sw) - 2), x1 = min(Wf - 1, (int)ceilf((float)(xc + 1) / sw) + 2);
+        const float* wc = w + (long long)c4 * 4 * kDwUpTaps;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int yy = y0; yy <= y1; ++yy) {
+            if (nearest_src(yy, sh, Hc) != yc) continue;
+            for (int xx = x0; xx <= x1; ++xx) {
+                if (nearest_src(xx, sw, Wc) != xc) continue;
+                for (int ky = 0; ky < 3; ++ky) {
+                    const int oy = yy + 1 - ky;
+                    if (oy < 0 || oy >= Hf) continue;
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const int ox = xx + 1 - kx;
+                        if (ox < 0 || ox >= Wf) continue;
+                        const float4 g = dy[(((long long)b * Hf + oy) * Wf + ox) * C4 + c4];
+                        const int t = ky * 3 + kx;
+                        s.x = fmaf(wc[t], g.x, s.x);
+                        s.y = fmaf(wc[kDwUpTaps + t], g.y, s.y);
+                        s.z = fmaf(wc[2 * kDwUpTaps + t], g.z, s.z);
+                        s.w = fmaf(wc[3 * kDwUpTaps + t], g.w, s.w);
+                    }
+                }
+            }
+        }
+        dcoarse[i] = s;
+    }
+}
+
+// dw[c][tap] = sum over the fine pixels of dy * up (and db[c] = sum dy): dw_wgrad_kernel's layout of the work -- grid (C4 blocks of 64
+// channel quads, pixel chunks), 4 pixel phases reduced through LDS, one partial per block and (channel, tap) added with an atomic
+// (one chunk in deterministic mode: the single partial adds to zero)
+__global__ void __launch_bounds__(256) dwup_wgrad_kernel(const float4* __restrict__ coarse, const float4* __restrict__ dy, int B, int Hc, int Wc, int Hf,
+                                                         int Wf, int C4, int pixels_per_block, float* __restrict__ dw, float* __restrict__ db) {
+    __shared__ float s_red[4][64][4];
+    const int cq = threadIdx.x & 63, ps = threadIdx.x >> 6;
+    const int c4 = blockIdx.x * 64 + cq;
+    const long long M = (long long)B * Hf * Wf;
+    const long long p0 = (long long)blockIdx.y * pixels_per_block, p1 = p0 + pixels_per_block < M ? p0 + pixels_per_block : M;
+    const float sh = (float)Hc / (float)Hf, sw = (float)Wc / (float)Wf;
+    float4 acc[kDwUpTaps];
+    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int t = 0; t < kDwUpTaps; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c4 < C4) {
+        for (long long p = p0 + ps; p < p1; p += 4) {
+            const int xo = (int)(p % Wf);
+            const int yo = (int)((p / Wf) % Hf);
+            const int b = (int)(p / ((long long)Wf * Hf));
+            const float4 g = dy[p * C4 + c4];
+            bsum.x += g.x; bsum.y += g.y; bsum.z += g.z; bsum.w += g.w;
+#pragma unroll
+            for (int t = 0; t < kDwUpTaps; ++t) {
+                const int iy = yo - 1 + t / 3, ix = xo - 1 + t % 3;
+                if (iy < 0 || iy >= Hf || ix < 0 || ix >= Wf) continue;
+                const float4 v = coarse[(((long long)b * Hc + nearest_src(iy, sh, Hc)) * Wc + nearest_src(ix, sw, Wc)) * C4 + c4];
+                acc[t].x = fmaf(g.x, v.x, acc[t].x);
+                acc[t].y = fmaf(g.y, v.y, acc[t].y);
+                acc[t].z = fmaf(g.z, v.z, acc[t].z);
+                acc[t].w = fmaf(g.w, v.w, acc[t].w);
+            }
+        }
+    }
+    for (int t = -1; t < kDwUpTaps; ++t) {
+        const float4 v = t < 0 ? bsum : acc[t < 0 ? 0 : t];
+        __syncthreads();
+        s_red[ps][cq][0] = v.x; s_red[ps][cq][1] = v.y; s_red[ps][cq][2] = v.z; s_red[ps][cq][3] = v.w;
+        __syncthreads();
+        if (ps == 0 && c4 < C4) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float sum = s_red[0][cq][e] + s_red[1][cq][e] + s_red[2][cq][e] + s_red[3][cq][e];
+                if (t < 0) { if (db) atomicAdd(db + c4 * 4 + e, sum); }
+                else atomicAdd(dw + (long long)(c4 * 4 + e) * kDwUpTaps + t, sum);
+            }
+        }
+    }
+}
+
+}  // namespace ssdk
+
+static int mp_check(const char* fn, int batch, int h, int w, int channels, int pad_bottom, int pad_right) {
+    SSDK_REQUIRE(batch > 0 && h > 0 && w > 0 && channels > 0 && channels % 4 == 0 && (pad_bottom == 0 || pad_bottom == 1) &&
+                     (pad_right == 0 || pad_right == 1),
+                 SSDK_E_INVALID, "%s: batch=%d H=%d W=%d C=%d (%% 4 == 0) pad_bottom=%d pad_right=%d (0 or 1)", fn, batch, h, w, channels,
+                 pad_bottom, pad_right);
+    SSDK_REQUIRE((h + pad_bottom) / 2 > 0 && (w + pad_right) / 2 > 0, SSDK_E_INVALID,
+                 "%s: a %d x %d map padded by (%d, %d) has no 2 x 2 window (zero-sized pooled output; torch's max_pool2d refuses it too)", fn, h,
+                 w, pad_bottom, pad_right);
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_maxpool2x2_fwd(const float* x, int batch, int h, int w, int channels, int pad_bottom, int pad_right, float* y, void* stream) {
+    int rc = mp_check("ssdk_maxpool2x2_fwd", batch, h, w, channels, pad_bottom, pad_right);
+    if (rc) return rc;
+    SSDK_REQUIRE(x && y && (((uintptr_t)x | (uintptr_t)y) & 15) == 0, SSDK_E_INVALID, "ssdk_maxpool2x2_fwd: null or unaligned pointer");
+    const int ho = (h + pad_bottom) / 2, wo = (w + pad_right) / 2;
+    hipLaunchKernelGGL(ssdk::maxpool2x2_kernel, dim3(stream_blocks((long long)batch * ho * wo * (channels / 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(x), batch, h, w, channels / 4, ho, wo, reinterpret_cast<float4*>(y));
+    SSDK_CHECK_LAUNCH("maxpool2x2_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_maxpool2x2_bwd(const float* x, const float* dy, int batch, int h, int w, int channels, int pad_bottom, int pad_right, float* dx,
+                                   void* stream) {
+    int rc = mp_check("ssdk_maxpool2x2_bwd", batch, h, w, channels, pad_bottom, pad_right);
+    if (rc) return rc;
+    SSDK_REQUIRE(x && dy && dx && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, SSDK_E_INVALID,
+                 "ssdk_maxpool2x2_bwd: null or unaligned pointer");
+    const int ho = (h + pad_bottom) / 2, wo = (w + pad_right) / 2;
+    hipLaunchKernelGGL(ssdk::maxpool2x2_bwd_kernel, dim3(stream_blocks((long long)batch * ho * wo * (channels / 4), 256)), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(dy), batch, h, w, channels / 4, ho, wo,
+                       reinterpret_cast<float4*>(dx));
+    SSDK_CHECK_LAUNCH("maxpool2x2_bwd_kernel");
+    return SSDK_OK;
+}
+
+static int cat_pieces(const char* fn, const float* const* pieces, const int* piece_channels, int n_pieces, long long rows, ssdk::CatPieces& ps) {
+    SSDK_REQUIRE(pieces && piece_channels && n_pieces > 0 && n_pieces <= ssdk::kMaxPieces && rows > 0, SSDK_E_INVALID,
+                 "%s: n_pieces=%d (1..%d) rows=%lld", fn, n_pieces, ssdk::kMaxPieces, rows);
+    ps = ssdk::CatPieces{};
+    ps.n = n_pieces;
+    for (int k = 0; k < n_pieces; ++k) {
+        SSDK_REQUIRE(piece_channels[k] > 0 && piece_channels[k] % 4 == 0, SSDK_E_INVALID, "%s: piece %d has %d channels (%% 4 == 0)", fn, k,
+                     piece_channels[k]);
+        SSDK_REQUIRE(pieces[k] && ((uintptr_t)pieces[k] & 15) == 0, SSDK_E_INVALID, "%s: piece %d is null or not 16-byte aligned", fn, k);
+        ps.p[k] = (float4*)pieces[k];
+        ps.c4[k] = piece_channels[k] / 4;
+        ps.off4[k + 1] = ps.off4[k] + ps.c4[k];
+    }
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_concat_channels_fwd(const float* const* pieces, const int* piece_channels, int n_pieces, long long rows, float* out, void* stream) {
+    ssdk::CatPieces ps;
+    int rc = cat_pieces("ssdk_concat_channels_fwd", pieces, piece_channels, n_pieces, rows, ps);
+    if (rc) return rc;
+    SSDK_REQUIRE(out && ((uintptr_t)out & 15) == 0, SSDK_E_INVALID, "ssdk_concat_channels_fwd: null or unaligned output");
+    hipLaunchKernelGGL(ssdk::concat_kernel, dim3(stream_blocks(rows * ps.off4[n_pieces], 256)), dim3(256), 0, (hipStream_t)stream, ps, rows,
+                       reinterpret_cast<float4*>(out));
+    SSDK_CHECK_LAUNCH("concat_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_concat_channels_bwd(const float* dout, const int* piece_channels, int n_pieces, long long rows, float* const* dpieces,
+                                        void* stream) {
+    ssdk::CatPieces ds;
+    int rc = cat_pieces("ssdk_concat_channels_bwd", (const float* const*)dpieces, piece_channels, n_pieces, rows, ds);
+    if (rc) return rc;
+    SSDK_REQUIRE(dout && ((uintptr_t)dout & 15) == 0, SSDK_E_INVALID, "ssdk_concat_channels_bwd: null or unaligned dout");
+    hipLaunchKernelGGL(ssdk::split_kernel, dim3(stream_blocks(rows * ds.off4[n_pieces], 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(dout), rows, ds);
+    SSDK_CHECK_LAUNCH("split_kernel");
+    return SSDK_OK;
+}
+
+static int dwup_check(const char* fn, int batch, int hc, int wc, int hf, int wf, int channels) {
+    SSDK_REQUIRE(batch > 0 && hc > 0 && wc > 0 && hf > 0 && wf > 0 && channels > 0 && channels % 4 == 0, SSDK_E_INVALID,
+                 "%s: batch=%d coarse %d x %d fine %d x %d C=%d (%% 4 == 0)", fn, batch, hc, wc, hf, wf, channels);
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_depthwise_upsample_conv2d_fwd(const float* coarse, const float* w, const float* bias, int batch, int hc, int wc, int hf, int wf,
+                                                  int channels, float* y, void* stream) {
+    int rc = dwup_check("ssdk_depthwise_upsample_conv2d_fwd", batch, hc, wc, hf, wf, channels);
+    if (rc) return rc;
+    SSDK_REQUIRE(coarse && w && y && (((uintptr_t)coarse | (uintptr_t)y | (uintptr_t)bias) & 15) == 0, SSDK_E_INVALID,
+                 "ssdk_depthwise_upsample_conv2d_fwd: null or unaligned pointer");
+    hipLaunchKernelGGL(ssdk::dwup_fwd_kernel, dim3(stream_blocks((long long)batch * hf * wf * (channels / 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(coarse), w, bias, batch, hc, wc, hf, wf, channels / 4, reinterpret_cast<float4*>(y));
+    SSDK_CHECK_LAUNCH("dwup_fwd_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_depthwise_upsample_conv2d_bwd(const float* coarse, const float* w, const float* dy, int batch, int hc, int wc, int hf, int wf,
+                                                  int channels, float* dcoarse, float* dw, float* db, void* stream) {
+    int rc = dwup_check("ssdk_depthwise_upsample_conv2d_bwd", batch, hc, wc, hf, wf, channels);
+    if (rc) return rc;
+    SSDK_REQUIRE(coarse && w && dy && (dcoarse || dw) && (((uintptr_t)coarse | (uintptr_t)dy | (uintptr_t)dcoarse) & 15) == 0, SSDK_E_INVALID,
+                 "ssdk_depthwise_upsample_conv2d_bwd: null or unaligned pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const int c4 = channels / 4;
+    if (dcoarse) {
+        hipLaunchKernelGGL(ssdk::dwup_dgrad_kernel, dim3(stream_blocks((long long)batch * hc * wc * c4, 256)), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(dy), w, batch, hc, wc, hf, wf, c4, reinterpret_cast<float4*>(dcoarse));
+        SSDK_CHECK_LAUNCH("dwup_dgrad_kernel");
+    }
+    if (dw) {
+        hipLaunchKernelGGL(ssdk::zero_small_kernel, dim3(8), dim3(256), 0, s, dw, (long long)channels * ssdk::kDwUpTaps, db, db ? (long long)channels : 0LL);
+        SSDK_CHECK_LAUNCH("zero_small_kernel");
+        const long long M = (long long)batch * hf * wf;
+        int chunks = (int)((M + 255) / 256);   // dw_wgrad_kernel's partials: >= 256 pixels per block, at most 512 per (channel, tap) ...
+        if (chunks > 512) chunks = 512;
+        if (ssdk::deterministic()) chunks = 1;  // ... and one in deterministic mode
+        const int ppb = (int)((M + chunks - 1) / chunks);
+        hipLaunchKernelGGL(ssdk::dwup_wgrad_kernel, dim3((unsigned)((c4 + 63) / 64), (unsigned)chunks), dim3(256), 0, s,
+                           reinterpret_cast<const float4*>(coarse), reinterpret_cast<const float4*>(dy), batch, hc, wc, hf, wf, c4, ppb, dw, db);
+        SSDK_CHECK_LAUNCH("dwup_wgrad_kernel");
+    }
+    return SSDK_OK;
+}

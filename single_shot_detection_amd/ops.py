@@ -1086,3 +1086,114 @@ class _DepthwiseFn(torch.autograd.Function):
 
 def depthwise_conv2d(x, weight, bias=None, stride=1, padding=0):
     return _DepthwiseFn.apply(x, weight, bias, int(stride), int(padding))
+
+
+# ---- depthwise feature pyramid (Tiny-DSOD D-FPN, bf/modules/features.py:123-212) ------------------------------------------------
+
+class _MaxPool2x2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(2)(F.pad(x, [0, pad_right, 0, pad_bottom])) (features.py:188-195): the pad is a real 0.0 in the max, its gradient is
+    dropped; the backward recomputes each window's maximum from x (ssdk_maxpool2x2_*)."""
+
+    @staticmethod
+    def forward(ctx, x, pad_bottom, pad_right):
+        _lib.require_cuda(x)
+        x = _nhwc(x)
+        B, C, H, W = x.shape
+        y = torch.empty((B, C, (H + pad_bottom) // 2, (W + pad_right) // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        _lib.check(_lib.lib().ssdk_maxpool2x2_fwd(_dp(x), B, H, W, C, pad_bottom, pad_right, _dp(y), _lib.current_stream()), 'ssdk_maxpool2x2_fwd')
+        ctx.save_for_backward(x)
+        ctx.pads = (pad_bottom, pad_right)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        B, C, H, W = x.shape
+        dy = _nhwc(dy)
+        dx = torch.empty_like(x, memory_format=torch.channels_last)
+        _lib.check(_lib.lib().ssdk_maxpool2x2_bwd(_dp(x), _dp(dy), B, H, W, C, ctx.pads[0], ctx.pads[1], _dp(dx), _lib.current_stream()),
+                   'ssdk_maxpool2x2_bwd')
+        return dx, None, None
+
+
+def maxpool2x2(x, pad_bottom=0, pad_right=0):
+    """2 x 2 / stride 2 max-pool of ``x`` zero-padded by ``pad_bottom`` rows and ``pad_right`` columns (0 or 1 each).  A map without a
+    single 2 x 2 window raises (as torch's max_pool2d does)."""
+    if x.shape[2] + int(pad_bottom) < 2 or x.shape[3] + int(pad_right) < 2:
+        raise ValueError(f'maxpool2x2: a {x.shape[2]} x {x.shape[3]} map padded by ({int(pad_bottom)}, {int(pad_right)}) has no 2 x 2 window '
+                         '(zero-sized pooled output)')
+    return _MaxPool2x2Fn.apply(x, int(pad_bottom), int(pad_right))
+
+
+class _ConcatFn(torch.autograd.Function):
+    """torch.cat(xs, dim=1) of NHWC maps (features.py:198); the backward writes each piece's gradient as its own contiguous map."""
+
+    @staticmethod
+    def forward(ctx, *xs):
+        import ctypes
+        _lib.require_cuda(*xs)
+        xs = [_nhwc(x) for x in xs]
+        B, _, H, W = xs[0].shape
+        assert all(x.shape[0] == B and x.shape[2:] == xs[0].shape[2:] for x in xs), [tuple(x.shape) for x in xs]
+        chans = [x.shape[1] for x in xs]
+        out = torch.empty((B, sum(chans), H, W), dtype=torch.float32, device=xs[0].device, memory_format=torch.channels_last)
+        ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+        cs = (ctypes.c_int * len(xs))(*chans)
+        _lib.check(_lib.lib().ssdk_concat_channels_fwd(ptrs, cs, len(xs), B * H * W, _dp(out), _lib.current_stream()), 'ssdk_concat_channels_fwd')
+        ctx.shapes = [tuple(x.shape) for x in xs]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        import ctypes
+        dout = _nhwc(dout)
+        B, _, H, W = dout.shape
+        ds = [torch.empty(s, dtype=torch.float32, device=dout.device, memory_format=torch.channels_last) for s in ctx.shapes]
+        ptrs = (ctypes.c_void_p * len(ds))(*[d.data_ptr() for d in ds])
+        cs = (ctypes.c_int * len(ds))(*[s[1] for s in ctx.shapes])
+        _lib.check(_lib.lib().ssdk_concat_channels_bwd(_dp(dout), cs, len(ds), B * H * W, ptrs, _lib.current_stream()), 'ssdk_concat_channels_bwd')
+        return tuple(ds)
+
+
+def concat_channels(xs):
+    """torch.cat(xs, dim=1) for up to 8 maps of one batch and size (channels of each % 4 == 0)."""
+    return _ConcatFn.apply(*xs)
+
+
+class _DepthwiseUpsampleFn(torch.autograd.Function):
+    """F.conv2d(F.interpolate(coarse, size=(hf, wf), mode='nearest'), weight, bias, padding=1, groups=C) (features.py:203-205, the
+    convolution of up_conv[i]) without the upsampled map: ssdk_depthwise_upsample_conv2d_*; weight is torch's [C, 1, 3, 3] parameter."""
+
+    @staticmethod
+    def forward(ctx, coarse, weight, bias, hf, wf):
+        lib = _lib.lib()
+        _lib.require_cuda(coarse, weight)
+        coarse = _nhwc(coarse)
+        B, C, Hc, Wc = coarse.shape
+        assert tuple(weight.shape) == (C, 1, 3, 3), tuple(weight.shape)
+        w = weight.float().contiguous()
+        b = None if bias is None else bias.float().contiguous()
+        y = torch.empty((B, C, hf, wf), dtype=torch.float32, device=coarse.device, memory_format=torch.channels_last)
+        _lib.check(lib.ssdk_depthwise_upsample_conv2d_fwd(_dp(coarse), _dp(w), _dp(b), B, Hc, Wc, hf, wf, C, _dp(y), _lib.current_stream()),
+                   'ssdk_depthwise_upsample_conv2d_fwd')
+        ctx.save_for_backward(coarse, w)
+        ctx.meta = (hf, wf, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        coarse, w = ctx.saved_tensors
+        hf, wf, has_bias = ctx.meta
+        B, C, Hc, Wc = coarse.shape
+        dy = _nhwc(dy)
+        dc = torch.empty_like(coarse, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w)
+        db = torch.empty((C,), dtype=torch.float32, device=coarse.device) if has_bias else None
+        _lib.check(_lib.lib().ssdk_depthwise_upsample_conv2d_bwd(_dp(coarse), _dp(w), _dp(dy), B, Hc, Wc, hf, wf, C, _dp(dc), _dp(dw), _dp(db),
+                                                                 _lib.current_stream()), 'ssdk_depthwise_upsample_conv2d_bwd')
+        return dc, dw, db, None, None
+
+
+def depthwise_upsample_conv2d(coarse, weight, bias, size):
+    """3 x 3 depthwise convolution (pad 1, stride 1) of ``F.interpolate(coarse, size, mode='nearest')``."""
+    return _DepthwiseUpsampleFn.apply(coarse, weight, bias, int(size[0]), int(size[1]))
