@@ -3726,6 +3726,62 @@ static void size_wgrad_splits(WgradGroup& wg, int n, int density_div) {
     wg.count = n;
     wg.total_blocks = begin;
 }
+// Launch-wide sizing of a grouped dense weight-gradient launch (the generic convolutions; deferred weight gradients put all layers of a
+// pyramid tail into one launch).  The per-problem rule above gives EVERY problem >= ~256 workgroups, as if it had the chip to itself:
+// the eight problems of the SSD-300 tail at batch 32 then share the launch with 1 648 workgroups -- 3.2 rounds on the 512 resident
+// slots, K chains of 5-20 slices between a prologue and a 64 KB tile epilogue: 159 us, 108 us sized this way.  Here the group as a whole gets a budget of about one round: every problem keeps
+// its 128-channel workgroups, every problem is cut into K chains of at most L slices -- workgroups in proportion to each problem's
+// MACs -- with L the smallest length at which the launch fits the budget (from the group's slice steps, tiles x 32-row slices, over the
+// budget upwards; never chains below a floor, never above the 64 slices of the rule above), and the problems are ordered longest chain
+// first.  A pure function of the shapes in the group: the workspace sizing calls it too.
+// order_out[old index] = new index of the problem in wg.p.  Groups of one problem keep the per-problem rule, and so does deterministic
+// mode: there the split count fixes the order of the sums, and a layer's weight gradient must come out with the same bits whether it
+// is computed alone or deferred into a group (eager step against the graphed hot path, tests/test_end_to_end_gpu.py).
+static int wgrad_knob(const char* name, int dflt) { const char* e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 ? v : dflt; }
+static void size_wgrad_group(WgradGroup& wg, int n, int* order_out = nullptr) {
+    static const bool launch_wide = getenv("SSDK_WGRAD_PER_PROBLEM") == nullptr;   // (measurement knob: the per-problem rule everywhere)
+    static const int budget = wgrad_knob("SSDK_WGRAD_BUDGET", 512);                // workgroups of the launch (measurement knob)
+    static const int min_chain = wgrad_knob("SSDK_WGRAD_MIN_CHAIN", 8);            // shortest K chain in slices (measurement knob)
+    for (int i = 0; i < n && order_out; ++i) order_out[i] = i;
+    if (n <= 1 || !launch_wide || deterministic()) { size_wgrad_splits(wg, n, 1); return; }
+    long long steps = 0;
+    int slices[kMaxProblems], tiles[kMaxProblems];
+    for (int i = 0; i < n; ++i) {
+        const WgradProblem& g = wg.p[i];
+        slices[i] = cdiv(g.B * g.Hout * g.Wout, 32);
+        tiles[i] = g.ksize * g.ksize * g.n_tiles * g.c_blocks;
+        steps += (long long)tiles[i] * slices[i];
+    }
+    // the shortest longest chain whose workgroups fit the budget (all resident at once, the launch ends with its longest chain)
+    auto splits_at = [&](int i, int chain) { return std::min(cdiv(slices[i], chain), std::max(1, slices[i] / min_chain)); };
+    int chain = (int)std::min<long long>(64, std::max<long long>(1, (steps + budget - 1) / budget));
+    for (; chain < 64; ++chain) {
+        long long blocks = 0;
+        for (int i = 0; i < n; ++i) blocks += (long long)tiles[i] * splits_at(i, chain);
+        if (blocks <= budget) break;
+    }
+    int idx[kMaxProblems], per[kMaxProblems];
+    for (int i = 0; i < n; ++i) {
+        int ks = splits_at(i, chain);
+        if (cdiv(slices[i], 64) > ks) ks = cdiv(slices[i], 64);
+        wg.p[i].k_splits = ks;
+        per[i] = cdiv(slices[i], ks);
+        int at = i;   // (stable insertion: longest chain first, ties in descriptor order)
+        while (at > 0 && per[idx[at - 1]] < per[i]) { idx[at] = idx[at - 1]; --at; }
+        idx[at] = i;
+    }
+    WgradProblem sorted[kMaxProblems];
+    int begin = 0;
+    for (int k = 0; k < n; ++k) {
+        sorted[k] = wg.p[idx[k]];
+        sorted[k].block_begin = begin;
+        begin += tiles[idx[k]] * sorted[k].k_splits;
+        if (order_out) order_out[idx[k]] = k;
+    }
+    for (int k = 0; k < n; ++k) wg.p[k] = sorted[k];
+    wg.count = n;
+    wg.total_blocks = begin;
+}
 
 // ---- the ordered pipeline (every level has anchor structure: a loc head with nb = n_loc / 4 anchor types, n_score = nb * C, C + 4 <= 128) ----
 // Per level the DEVICE picks the form (anchor_plan_kernel): 2 = anchor rows (see "Ordered anchor-row backward" above) when the rows fit the
@@ -4451,15 +4507,27 @@ static WgradProblem conv_wgrad_problem(const ssdk_conv_desc& d, int batch) {
     g.c_blocks = cdiv(g.c_tiles32, kMaxTN);
     return g;
 }
-static int conv_wgrad_splits(const ssdk_conv_desc& d, int batch) {
-    WgradGroup one{};
-    one.p[0] = conv_wgrad_problem(d, batch);
-    size_wgrad_splits(one, 1, 1);
-    return one.p[0].k_splits;
+// K splits of every weight-gradient problem of a grouped call as ssdk_conv2d_bwd sizes them (splits[i] = 0 for a descriptor without dw):
+// the launch and the workspace sizing of the deterministic copies both come through here
+static void conv_wgrad_splits(const ssdk_conv_desc* descs, int n, int batch, int* splits) {
+    WgradGroup wg{};
+    int of[kMaxProblems], order[kMaxProblems], m = 0;
+    for (int i = 0; i < n; ++i) {
+        splits[i] = 0;
+        of[i] = -1;
+        if (!descs[i].dw || descs[i].ksize <= 0 || descs[i].stride <= 0) continue;
+        of[i] = m;
+        wg.p[m++] = conv_wgrad_problem(descs[i], batch);
+    }
+    size_wgrad_group(wg, m, order);
+    for (int i = 0; i < n; ++i)
+        if (of[i] >= 0) splits[i] = wg.p[order[of[i]]].k_splits;
 }
 
 static size_t conv2d_bwd_ws_bytes(const ssdk_conv_desc* descs, int n, int batch, bool fast) {
     size_t total = 0;
+    int splits[kMaxProblems] = {};
+    if (deterministic() && batch > 0 && n > 0 && n <= kMaxProblems) conv_wgrad_splits(descs, n, batch, splits);   // (any other n is refused by the call itself)
     for (int i = 0; i < n; ++i) {
         const ssdk_conv_desc& d = descs[i];
         const size_t wsz = (size_t)d.cin * d.ksize * d.ksize * (size_t)d.cout;
@@ -4468,7 +4536,7 @@ static size_t conv2d_bwd_ws_bytes(const ssdk_conv_desc* descs, int n, int batch,
         if (d.dx && d.stride > 1 && d.ksize > 0 && batch > 0)   // the contribution rows of the strided data gradient [B * Hout * Wout][taps * Cin]
             total += align_up((size_t)batch * out_dim(d.hin, d.ksize, d.stride, d.pad) * out_dim(d.win, d.ksize, d.stride, d.pad) * d.ksize * d.ksize * d.cin * sizeof(float), 256);
         if (deterministic() && batch > 0 && d.ksize > 0 && d.stride > 0) {   // K-split copies of dw, per-workgroup column sums of db
-            if (d.dw) total += align_up((size_t)conv_wgrad_splits(d, batch) * wsz * sizeof(float), 256);
+            if (d.dw && i < kMaxProblems) total += align_up((size_t)splits[i] * wsz * sizeof(float), 256);
             if (d.db) total += align_up((size_t)kColsumBlocks * d.cout * sizeof(float), 256);
         }
     }
@@ -4509,7 +4577,9 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
     int n_rowsT = 0, sd_blocks = 0;
     // strided data gradients: contribution rows + sum pass (ordered, no zero-fill) in deterministic mode; otherwise the atomic scatter
     // form, which measured 15-35 us faster per SSD-300 step (3.055 against 3.07-3.09 ms: the small maps' row GEMMs underfill the chip);
-    // SSDK_CONV_STRIDED_ORDERED=1 takes the ordered form everywhere (measurement knob).  Round 4's deterministic form -- the
+    // SSDK_CONV_STRIDED_ORDERED=1 takes the ordered form everywhere (measurement knob; the ordered form for the one layer whose T GEMM
+    // fills the chip -- 3 x 3 / 2 256 -> 512 at 18 x 18, batch 32: 378 tiles -- and the scatter form for the rest: 2.921 against 2.920 ms
+    // per step, medians of four interleaved runs: no gain, not kept).  Round 4's deterministic form -- the
     // output-stationary gather GEMM with three of four (pixel, tap) pairs masked -- cost 760 us per step where this costs 190.
     static const bool strided_scatter = getenv("SSDK_CONV_STRIDED_ORDERED") == nullptr;
     WgradGroup wg{};
@@ -4520,7 +4590,8 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
     const bool det = deterministic();
     float* dw_part[kMaxProblems] = {};
     float* db_part[kMaxProblems] = {};
-    int wg_of[kMaxProblems];
+    int wg_of[kMaxProblems], dw_splits[kMaxProblems] = {};
+    if (det && batch > 0) conv_wgrad_splits(descs, n, batch, dw_splits);   // (what size_wgrad_group will give the launch below)
     // fast mode (ssdk_conv2d_bwd_fast): stride-1 data gradients on the split-bf16 kernel -- the forward convolution of dy with the
     // mirrored kernel, whose two bf16 planes are split from the re-laid-out weights [cin][tap][cout] with the taps reversed
     ConvProblem fdg[kMaxProblems];
@@ -4628,7 +4699,7 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
             g.dy = d.dy;
             g.dw0 = d.dw; g.dw1 = nullptr;
             if (det) {   // every K split stores its own copy (added in split order below)
-                dw_part[i] = carve.take<float>((size_t)conv_wgrad_splits(d, batch) * d.cout * taps * d.cin);
+                dw_part[i] = carve.take<float>((size_t)dw_splits[i] * d.cout * taps * d.cin);
                 g.dw0 = dw_part[i];
                 g.det_stride = (long long)d.cout * taps * d.cin;
             }
@@ -4707,7 +4778,10 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
         if (rc) return rc;
     }
     if (n_wgrad) {
-        size_wgrad_splits(wg, n_wgrad, 1);
+        int order[kMaxProblems];
+        size_wgrad_group(wg, n_wgrad, order);   // (reorders wg.p: longest K chain first)
+        for (int i = 0; i < n; ++i)
+            if (wg_of[i] >= 0) wg_of[i] = order[wg_of[i]];
         { int rc2 = launch_wgrad(wg, s, fast); if (rc2) return rc2; }
     }
     if (det) {
