@@ -470,6 +470,9 @@ int ssdk_conv2d_transpose_weights(const ssdk_conv_desc* descs, int n, float* con
 int ssdk_relu_bwd(const float* y, const float* dy, long long n, float* dx, void* stream);
 
 size_t ssdk_batchnorm_workspace_bytes(int channels); /* = the [2 * channels + 2] doubles of a `sums` buffer (below), 256-byte rounded */
+/* Every entry point of the BatchNorm family moves float4s: channels % 4 == 0 and 16-byte aligned x / y / dy / dx, SSDK_E_UNSUPPORTED
+ * otherwise.  The composed entry points (_fwd, _bwd, _fwd_chained, _bwd_chained) check all of it before their first launch: a call that
+ * is refused has written nothing. */
 /*
  * torch.nn.BatchNorm2d forward on [rows = batch*H*W][channels] (NHWC), optional fused ReLU after it (conv.py:33-35).
  * training != 0: batch statistics (biased variance), running_mean / running_var updated with `momentum` (unbiased

@@ -288,9 +288,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvProblem& g, const f32x16
 #pragma unroll
     for (int j = 0; j < NT; ++j) asm volatile("" : "+v"(biasj[j]));
     double* const stats = (!split && s_red) ? g.stats : nullptr;   // (uniform over the workgroup)
-    float cs1[NT], cs2[NT];
+    // (fp64 from the first add on: the norm's variance is E[x^2] - mean^2, and fp32 partial sums lose it for a channel whose mean is many
+    // standard deviations -- DESIGN.md, "BatchNorm statistics: conditioning"; the square of an fp32 value is exact in fp64)
+    double cs1[NT], cs2[NT];
 #pragma unroll
-    for (int j = 0; j < NT; ++j) cs1[j] = cs2[j] = 0.0f;
+    for (int j = 0; j < NT; ++j) cs1[j] = cs2[j] = 0.0;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         const int src = (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -309,8 +311,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvProblem& g, const f32x16
             } else {
                 const float out = relu ? fmaxf(v, 0.0f) : v;
                 *dst = out;
-                cs1[j] += out;
-                cs2[j] += out * out;
+                if (stats) {
+                    const double o = (double)out;
+                    cs1[j] += o;
+                    cs2[j] += o * o;
+                }
             }
         }
     }
@@ -354,12 +359,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvProblem& g, const f32x16
             cs1[j] += __shfl_xor(cs1[j], 32, kWave);
             cs2[j] += __shfl_xor(cs2[j], 32, kWave);
         }
+        double* const d_red = reinterpret_cast<double*>(s_red);   // (waves * NT * 64 doubles <= 8 KB of the 16 KB A stage)
         __syncthreads();
         if (h == 0) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                s_red[((wave * NT + j) * 32 + r32) * 2 + 0] = cs1[j];
-                s_red[((wave * NT + j) * 32 + r32) * 2 + 1] = cs2[j];
+                d_red[((wave * NT + j) * 32 + r32) * 2 + 0] = cs1[j];
+                d_red[((wave * NT + j) * 32 + r32) * 2 + 1] = cs2[j];
             }
         }
         __syncthreads();
@@ -367,10 +373,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvProblem& g, const f32x16
         for (int q = t; q < NT * 32; q += waves * 64) {
             const int j = q >> 5, c = q & 31, n = n_begin + j * 32 + c;
             if (j < tn && n < n0) {
-                float a = 0.0f, b = 0.0f;
-                for (int w = 0; w < waves; ++w) { a += s_red[((w * NT + j) * 32 + c) * 2 + 0]; b += s_red[((w * NT + j) * 32 + c) * 2 + 1]; }
-                atomicAdd(stats + n, (double)a);
-                atomicAdd(stats + n0 + n, (double)b);
+                double a = 0.0, b = 0.0;
+                for (int w = 0; w < waves; ++w) { a += d_red[((w * NT + j) * 32 + c) * 2 + 0]; b += d_red[((w * NT + j) * 32 + c) * 2 + 1]; }
+                atomicAdd(stats + n, a);
+                atomicAdd(stats + n0 + n, b);
             }
         }
         if (m_base == 0 && n_begin == 0 && t == 0) stats[2 * n0] = (double)M;
@@ -810,6 +816,7 @@ __device__ __forceinline__ void dma_tile(const ConvProblem& g, int pi, int m_til
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[j][e] = nanv;
     }
+    static_assert(sizeof(s_a0) >= sizeof(double) * WAVES * MAXTN * 64, "the statistics epilogue folds its fp64 column sums through the A stage");
     conv_epilogue<SCATTER>(g, acc, m_base, wave, r32, h, tn, n_begin, M, N, hw, ksp, (!MIRROR && !SCATTER) ? s_a0 : nullptr, WAVES,
                            half ? tn - 1 : -1);   // (a stream-K owner too: the fix-up ends behind a barrier)
     PHASE(3)

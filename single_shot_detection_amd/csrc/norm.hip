@@ -35,11 +35,17 @@ static inline int bn_rows_per_block(long long rows) {
 
 // MODE 0: s0 = sum x, s1 = sum x^2.   MODE 1 (backward): s0 = sum dy', s1 = sum dy' * xhat, dy' = relu ? dy * (y > 0) : dy
 // Workgroup = 64 rows; wave w takes rows w, w+4, ...; lane l owns float4 columns l, l+64, ... (whole 1 KB lines per wave).
+// MODE 0 accumulates in fp64 from the first add on: the variance is E[x^2] - mean^2, and with fp32 partial sums a channel whose mean is
+// 100 standard deviations lost four digits of it ("BatchNorm statistics: conditioning").  The square of an fp32 value is exact
+// in fp64; the kernel streams from HBM and the fp64 adds hide behind the loads.  MODE 1 sums centred, scaled values and stays in fp32.
+template <typename T> struct bn_acc4 { T x, y, z, w; };
 template <int MODE>
 __global__ void __launch_bounds__(256) bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
                                                         long long rows, int rows_per_block, int C, const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, int relu, double* __restrict__ sums) {
-    __shared__ float4 s_part[2][4][64];
+    using acc_t = typename std::conditional<MODE == 0, double, float>::type;
+    using acc4 = bn_acc4<acc_t>;
+    __shared__ acc4 s_part[2][4][64];   // (16 KB in MODE 0, 8 KB in MODE 1)
     const long long r0 = (long long)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C4 = C >> 2;
@@ -52,9 +58,9 @@ __global__ void __launch_bounds__(256) bn_reduce_kernel(const float* __restrict_
     if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = (double)rows;   // (slot 2C: the count behind the sums)
     for (int cbase = 0; cbase < C4; cbase += 64) {
         const int c4 = packed ? lane - sub * C4 : cbase + lane;
-        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+        acc4 a0 = {0, 0, 0, 0}, a1 = a0;
         if (c4 < C4) {
-            float4 m4 = a0, rs4 = a0;
+            float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), rs4 = m4;
             if (MODE == 1) { m4 = reinterpret_cast<const float4*>(mean)[c4]; rs4 = reinterpret_cast<const float4*>(rstd)[c4]; }
             // four row groups per trip, all their loads issued before the first is consumed (a row per trip made every wave wait one
             // memory round trip per row: 10-24 us on the small pyramid maps); rows past the end re-read the last row, weight 0
@@ -77,8 +83,9 @@ __global__ void __launch_bounds__(256) bn_reduce_kernel(const float* __restrict_
                     if (wgt[u] == 0.0f) continue;
                     const float4 xu = xv[u];
                     if (MODE == 0) {
-                        a0.x += xu.x; a0.y += xu.y; a0.z += xu.z; a0.w += xu.w;
-                        a1.x += xu.x * xu.x; a1.y += xu.y * xu.y; a1.z += xu.z * xu.z; a1.w += xu.w * xu.w;
+                        const acc_t x0 = xu.x, x1 = xu.y, x2 = xu.z, x3 = xu.w;
+                        a0.x += x0; a0.y += x1; a0.z += x2; a0.w += x3;
+                        a1.x += x0 * x0; a1.y += x1 * x1; a1.z += x2 * x2; a1.w += x3 * x3;
                     } else {
                         float4 g = gv[u];
                         if (relu) {
@@ -105,8 +112,8 @@ __global__ void __launch_bounds__(256) bn_reduce_kernel(const float* __restrict_
         s_part[1][wave][lane] = a1;
         __syncthreads();
         if (wave < 2 && (packed ? lane < C4 : c4 < C4)) {  // wave 0 folds the s0 partials, wave 1 the s1 partials
-            float4 t = s_part[wave][0][lane];
-            for (int w = 1; w < 4; ++w) { const float4 u = s_part[wave][w][lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+            acc4 t = s_part[wave][0][lane];
+            for (int w = 1; w < 4; ++w) { const acc4 u = s_part[wave][w][lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
             double* dst = sums + (size_t)wave * C + (size_t)(packed ? lane : c4) * 4;
             atomicAdd(dst + 0, (double)t.x); atomicAdd(dst + 1, (double)t.y); atomicAdd(dst + 2, (double)t.z); atomicAdd(dst + 3, (double)t.w);
         }
@@ -126,6 +133,10 @@ __device__ __forceinline__ void stats_from_sums(const double* sums, double inv_n
     rs = (float)rsqrt(var + (double)eps);
     var_out = (float)(var * unbias);
 }
+
+// evaluation mode: 1 / sqrt(running_var + eps), rounded once (the fp32 form -- add, square root, division: three roundings -- was up to
+// 2 ulp off, which a beta that cancels most of gamma * xhat turns into several ulp of y)
+__device__ __forceinline__ float eval_rstd(float running_var, float eps) { return (float)rsqrt((double)running_var + (double)eps); }
 
 __global__ void __launch_bounds__(256) bn_apply_kernel(const float4* __restrict__ x, long long n4, int C4, const float4* __restrict__ mean,
                                                        const float4* __restrict__ rstd, const float4* __restrict__ gamma,
@@ -154,7 +165,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float4* __restrict_
     if (!sums && !mean && blockIdx.x == 0)   // evaluation mode: what the backward of a frozen norm needs
         for (int c = threadIdx.x; c < C; c += blockDim.x) {
             save_mean[c] = running_mean[c];
-            save_rstd[c] = 1.0f / sqrtf(running_var[c] + eps);
+            save_rstd[c] = eval_rstd(running_var[c], eps);
         }
     // A thread's four channels do not change over its grid-stride trips when the stride is a multiple of the row length (always for
     // power-of-two C): mean / rstd -- four fp64 divisions and square roots from the sums -- gamma and beta are then worked out ONCE per
@@ -175,7 +186,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float4* __restrict_
         } else {   // evaluation mode: the running statistics (torch: 1 / sqrt(running_var + eps))
             m = reinterpret_cast<const float4*>(running_mean)[c];
             const float4 rv = reinterpret_cast<const float4*>(running_var)[c];
-            rs = make_float4(1.0f / sqrtf(rv.x + eps), 1.0f / sqrtf(rv.y + eps), 1.0f / sqrtf(rv.z + eps), 1.0f / sqrtf(rv.w + eps));
+            rs = make_float4(eval_rstd(rv.x, eps), eval_rstd(rv.y, eps), eval_rstd(rv.z, eps), eval_rstd(rv.w, eps));
         }
         ga = gamma ? gamma[c] : make_float4(1.f, 1.f, 1.f, 1.f);
         be = beta ? beta[c] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -279,6 +290,20 @@ using namespace ssdk;
 // is two fill kernels in the runtime, one for the 16-byte aligned part and one for the tail)
 extern "C" size_t ssdk_batchnorm_workspace_bytes(int channels) { return align_up(((size_t)2 * channels + 2) * sizeof(double), 256); }
 
+// The composed entry points launch twice: everything either half would refuse is refused here, before the first launch.
+static int bn_fwd_check(const char* fn, const float* x, const float* y, const float* save_mean, const float* save_rstd, long long rows, int channels) {
+    SSDK_REQUIRE(x && y && save_mean && save_rstd && rows > 0 && channels > 0, SSDK_E_INVALID, "%s: bad arguments", fn);
+    SSDK_REQUIRE(channels % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0, SSDK_E_UNSUPPORTED, "%s: channels %% 4 != 0 or buffers not 16-byte aligned", fn);
+    return SSDK_OK;
+}
+static int bn_bwd_check(const char* fn, const float* x, const float* y, const float* dy, const float* dx, const float* save_mean, const float* save_rstd,
+                        long long rows, int channels, int relu) {
+    SSDK_REQUIRE(x && dy && dx && save_mean && save_rstd && rows > 0 && channels > 0 && (!(relu & 1) || y), SSDK_E_INVALID, "%s: bad arguments", fn);
+    SSDK_REQUIRE(channels % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)y) & 15) == 0, SSDK_E_UNSUPPORTED,
+                 "%s: channels %% 4 != 0 or buffers not 16-byte aligned", fn);
+    return SSDK_OK;
+}
+
 static int bn_stats(const float* x, long long rows, int channels, double* sums, bool zero_first, void* stream) {
     SSDK_REQUIRE(x && sums && rows > 0 && channels > 0, SSDK_E_INVALID, "ssdk_batchnorm_stats: bad arguments");
     SSDK_REQUIRE(channels % 4 == 0 && ((uintptr_t)x & 15) == 0, SSDK_E_UNSUPPORTED, "ssdk_batchnorm_stats: channels %% 4 != 0 or x not 16-byte aligned");
@@ -329,6 +354,7 @@ extern "C" int ssdk_batchnorm_fwd_chained(const float* x, long long rows, int ch
                                           int relu, float* y, float* save_mean, float* save_rstd, double* sums, double* zero_after,
                                           void* stream) {
     SSDK_REQUIRE(sums && sums != zero_after, SSDK_E_INVALID, "ssdk_batchnorm_fwd_chained: sums missing or equal to zero_after");
+    if (const int bad = bn_fwd_check("ssdk_batchnorm_fwd_chained", x, y, save_mean, save_rstd, rows, channels)) return bad;
     const int rc = bn_stats(x, rows, channels, sums, false, stream);
     if (rc) return rc;
     return bn_apply(x, rows, channels, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, relu, y, save_mean, save_rstd,
@@ -378,6 +404,8 @@ static int bn_bwd_stats(const float* x, const float* y, const float* dy, long lo
     relu &= 1;   // (bit 1 -- the norm's input is a ReLU output -- concerns dx only: the sums are over the gradient of the norm's OUTPUT)
     SSDK_REQUIRE(x && dy && sums && save_mean && save_rstd && rows > 0 && channels > 0 && (!relu || y), SSDK_E_INVALID,
                  "ssdk_batchnorm_bwd_stats: bad arguments");
+    SSDK_REQUIRE(channels % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)y) & 15) == 0, SSDK_E_UNSUPPORTED,
+                 "ssdk_batchnorm_bwd_stats: channels %% 4 != 0 or buffers not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (zero_first) SSDK_CHECK_HIP(zero_async(sums, sizeof(double) * (2 * (size_t)channels + 2), s));
     const int rpb = bn_rows_per_block(rows);
@@ -423,6 +451,7 @@ extern "C" int ssdk_batchnorm_bwd_chained(const float* x, const float* y, const 
                                           const float* save_mean, const float* save_rstd, int relu, float* dx, float* dgamma, float* dbeta,
                                           double* sums, double* zero_after, void* stream) {
     SSDK_REQUIRE(sums && sums != zero_after && dx, SSDK_E_INVALID, "ssdk_batchnorm_bwd_chained: bad arguments");
+    if (const int bad = bn_bwd_check("ssdk_batchnorm_bwd_chained", x, y, dy, dx, save_mean, save_rstd, rows, channels, relu)) return bad;
     const int rc = bn_bwd_stats(x, y, dy, rows, channels, save_mean, save_rstd, relu, sums, false, stream);
     if (rc) return rc;
     return bn_bwd_apply(x, y, dy, rows, channels, gamma, save_mean, save_rstd, relu, 1, sums, nullptr, nullptr, dx, dgamma, dbeta, zero_after, stream);
@@ -431,7 +460,7 @@ extern "C" int ssdk_batchnorm_bwd_chained(const float* x, const float* y, const 
 extern "C" int ssdk_batchnorm_bwd(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
                                   const float* save_mean, const float* save_rstd, int relu, int training, float* dx, float* dgamma,
                                   float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
-    SSDK_REQUIRE(x && dy && dx && save_mean && save_rstd && rows > 0 && channels > 0 && (!(relu & 1) || y), SSDK_E_INVALID, "ssdk_batchnorm_bwd: bad arguments");
+    if (const int bad = bn_bwd_check("ssdk_batchnorm_bwd", x, y, dy, dx, save_mean, save_rstd, rows, channels, relu)) return bad;
     SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_batchnorm_workspace_bytes(channels), SSDK_E_WORKSPACE, "ssdk_batchnorm_bwd: workspace too small");
     const int rc = ssdk_batchnorm_bwd_stats(x, y, dy, rows, channels, save_mean, save_rstd, relu, (double*)workspace, stream);
     if (rc) return rc;
