@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 116
+#define SSDK_VERSION 117
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -35,6 +35,9 @@ extern "C" {
 /* detection/matcher.py:4-5 */
 #define SSDK_NOT_MATCHED (-2)
 #define SSDK_IGNORE (-1)
+/* force stage of ssdk_encode_ground_truth_ex */
+#define SSDK_FORCE_MATCH_PER_PREDICTION 0 /* matcher.py:52-54: every box's best anchor, the highest box index wins a shared one */
+#define SSDK_FORCE_MATCH_BIPARTITE 1      /* matcher.py:7-31: greedy bipartite matching, every box an anchor of its own */
 
 /* classification loss kinds (bf/modules/losses.py) */
 #define SSDK_CLS_CROSS_ENTROPY 0 /* torch.nn.CrossEntropyLoss(reduction='sum', ignore_index=-1), losses.py:4 */
@@ -157,6 +160,40 @@ size_t ssdk_match_per_prediction_workspace_bytes(int num_boxes);
 int ssdk_match_per_prediction(const float* weights, int num_boxes, int num_anchors, float matched_threshold,
                               float unmatched_threshold, int force_match_for_each_target, int64_t* box_idx, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+size_t ssdk_match_bipartite_workspace_bytes(int num_boxes, int num_anchors);
+/*
+ * detection/matcher.py:7-31 match_bipartite on a given weight matrix: weights DEV [num_boxes, num_anchors].  num_boxes times: the
+ * argmax of the whole matrix (first flat index on ties: the lowest row, then the lowest column) gives that row that column, then the
+ * column and the row are zeroed.  anchor_idx DEV int64 [num_boxes] (the reference's box_idx is arange(num_boxes)); num_matched DEV
+ * int32 [1]: the rounds whose maximum was above 0.
+ *   EXHAUSTION: once the maximum is 0 (two boxes whose only positive entry is the same column, or num_boxes > num_anchors) every later
+ *   round of the reference lands on flat index 0: it sets anchor_idx[0] = 0 and leaves the other left-over boxes' entries
+ *   uninitialised.  Reproduced: anchor_idx[0] == 0 whenever a box was left over; the left-over boxes' entries are -1 here.
+ *   inplace != 0: `weights` is the working matrix and is left as the reference leaves it (all zeros when every box got an anchor; after
+ *   exhaustion the same zeroed rows and columns, row 0 and column 0 included).  inplace == 0: `weights` is only read (a copy in the
+ *   workspace is matched).
+ * NaN entries rank below everything (the reference asserts weights.max(dim=1) > 0 first, which a NaN row fails; that assert, with its
+ * sync, is the Python wrapper's).  One workgroup; ends for any input.
+ */
+int ssdk_match_bipartite(float* weights, int num_boxes, int num_anchors, int inplace, int64_t* anchor_idx, int32_t* num_matched,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+size_t ssdk_encode_ground_truth_ex_workspace_bytes(int batch, int total_gt, int force_match);
+/*
+ * ssdk_encode_ground_truth with the force stage chosen by `force_match` (the other arguments as there):
+ *   SSDK_FORCE_MATCH_PER_PREDICTION  ssdk_encode_ground_truth itself.
+ *   SSDK_FORCE_MATCH_BIPARTITE       box_idx = match_per_prediction(iou, ..., force_match_for_each_target=False) (matcher.py:45-50), then
+ *                                    box_idx[anchor_idx] = arange(G) with anchor_idx from match_bipartite(iou) (matcher.py:7-31), per
+ *                                    image: one more launch (one workgroup per image) between the two of the default form; still
+ *                                    nothing [G, A]-shaped.  Unlike ssdk_match_bipartite, the stage STOPS at the first maximum that is
+ *                                    not above 0 (NaN included): the boxes left over get no forced anchor and box 0 keeps its own.
+ *                                    Any number of boxes per image; num_anchors <= 262144 (SSDK_E_UNSUPPORTED above).
+ */
+int ssdk_encode_ground_truth_ex(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                const float* anchors, int num_anchors, float matched_threshold, float unmatched_threshold,
+                                int force_match, float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes,
+                                void* stream);
 
 /* ---- sampler + loss (S1 + L1 + L2 + L3) ----------------------------------------------------------------------- */
 

@@ -15,6 +15,8 @@
 //                         and writes the 24-byte target row through an LDS tile so HBM sees whole 8-byte lanes of a
 //                         contiguous 6 KB block.  The target is written exactly once: B*A*24 bytes, the
 //                         algorithmic minimum for this path.
+// Opt-in (ssdk_encode_ground_truth_ex, SSDK_FORCE_MATCH_BIPARTITE): bipartite_resolve_kernel between the two, one workgroup per image,
+// replaces the force-match rule by greedy bipartite matching (matcher.py:7-31); see further down.
 // IoU is computed op for op like the reference (this TU is built -ffp-contract=off, IEEE divide) so that
 // assignments are bit-exact.
 #include "common.h"
@@ -196,6 +198,191 @@ __global__ void __launch_bounds__(kAssignThreads) mpp_assign_kernel(const float*
     box_idx[a] = bi;
 }
 
+
+// ---- detection/matcher.py:7-31 match_bipartite --------------------------------------------------------------------------------------
+// Greedy bipartite matching: repeat { argmax of the whole matrix; that row gets that column; zero the column and the row }.  Both forms
+// below keep ONE 64-bit key per box -- its best remaining (value, ~column) -- and redo a box's row only when its column was just taken,
+// so a round costs one reduction over the boxes plus the rescans of the boxes that collided.  One workgroup owns a whole problem (an
+// image, or the matrix): no workgroup waits on another, every loop is counted by G or A, and a NaN never wins a comparison.
+constexpr int kBipThreads = 1024;
+constexpr int kBipWaves = kBipThreads / kWave;
+constexpr int kBipLdsBoxes = 1024;        // per image: more boxes than this keep their keys in the workspace instead of LDS (same code, flat pointers)
+constexpr int kBipMaxAnchors = 262144;    // the taken-column bit mask of the fused form is 32 KB of LDS
+constexpr unsigned kOrdZero = 0x80000000u;  // ord_f32(0.0f)
+
+__device__ __forceinline__ unsigned key_hi(unsigned long long k) { return (unsigned)(k >> 32); }
+__device__ __forceinline__ int key_col(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); }
+__device__ __forceinline__ unsigned long long make_key(unsigned hi, int idx) { return ((unsigned long long)hi << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)idx); }
+// Order-preserving bits of any float: -inf < ... < -0 == +0 < ... < +inf, all above 0; NaN -> 0, below everything (it never wins).
+__device__ __forceinline__ unsigned ord_f32(float v) {
+    if (v != v) return 0u;
+    if (v == 0.0f) return kOrdZero;
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// Maximum of a key over the workgroup, returned to every thread.  `red` = LDS [kBipWaves]; two barriers, `red` is free again afterwards.
+__device__ __forceinline__ unsigned long long bip_block_max(unsigned long long k, unsigned long long* red) {
+    k = wave_allreduce(k, OpMaxU64());
+    if (lane_id() == 0) red[threadIdx.x >> 6] = k;
+    __syncthreads();
+    unsigned long long r = red[0];
+#pragma unroll
+    for (int i = 1; i < kBipWaves; ++i) { const unsigned long long t = red[i]; r = t > r ? t : r; }
+    __syncthreads();
+    return r;
+}
+// The workgroup rescans n rows (rows[j], or j itself when rows == NULL): `sweep(row)` is every thread's best key over its share of the
+// row's columns; the row's key (largest value, then lowest column) goes to keys[row].  Rows go in batches of kBipWaves with two barriers
+// per batch: each wave leaves its partial key per row in LDS, then wave j folds row j's partials.
+template <typename Sweep>
+__device__ __forceinline__ void bip_rescan(const int* rows, int n, unsigned long long* keys, unsigned long long (*part)[kBipWaves], Sweep sweep) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    for (int base = 0; base < n; base += kBipWaves) {
+        const int m = min(kBipWaves, n - base);
+        for (int j = 0; j < m; ++j) {
+            const int r = rows ? rows[base + j] : base + j;
+            const unsigned long long k = wave_allreduce(sweep(r), OpMaxU64());
+            if (lane == 0) part[j][wave] = k;
+        }
+        __syncthreads();
+        if (wave < m) {
+            unsigned long long k = lane < kBipWaves ? part[wave][lane] : 0ull;
+            k = wave_allreduce(k, OpMaxU64());
+            if (lane == 0) keys[rows ? rows[base + wave] : base + wave] = k;
+        }
+        __syncthreads();
+    }
+}
+
+// Fused form (the force stage of TargetAssigner(force_match='bipartite')): one workgroup per image, between gt_argmax_kernel and
+// assign_kernel.  It takes every box's best (iou, ~anchor) key from gt_best, resolves the collisions and writes the result back in key
+// form into gt_best[g * segs + 0] (the other segments' slots and the boxes without a forced anchor: 0, which decodes to anchor -1), so
+// assign_kernel runs unchanged.  A rescan recomputes the box's IoUs exactly as gt_argmax_kernel does, skipping the taken anchors.  The
+// stage ends at the first maximum that is not above 0 (NaN counts as not above 0): the boxes left over get no forced anchor.
+__global__ void __launch_bounds__(kBipThreads) bipartite_resolve_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                        const float4* __restrict__ anchors, int A, unsigned long long* gt_best, int segs,
+                                                                        unsigned long long* spill_keys, int* spill_rows) {
+    __shared__ unsigned long long s_key[kBipLdsBoxes];
+    __shared__ int s_rows[kBipLdsBoxes];
+    __shared__ unsigned s_taken[kBipMaxAnchors / 32];
+    __shared__ unsigned long long s_red[kBipWaves];
+    __shared__ unsigned long long s_part[kBipWaves][kBipWaves];
+    __shared__ int s_n;
+    const int i = blockIdx.x;
+    const int g0 = gt_off[i], G = gt_off[i + 1] - g0;
+    if (G <= 0) return;
+    unsigned long long* keys = G <= kBipLdsBoxes ? s_key : spill_keys + g0;
+    int* rows = G <= kBipLdsBoxes ? s_rows : spill_rows + g0;
+    for (int w = threadIdx.x; w < (A + 31) / 32; w += kBipThreads) s_taken[w] = 0u;
+    for (int r = threadIdx.x; r < G; r += kBipThreads) {
+        unsigned long long* slot = gt_best + (size_t)(g0 + r) * segs;
+        unsigned long long key = slot[0];
+        slot[0] = 0ull;
+        for (int q = 1; q < segs; ++q) { const unsigned long long k2 = slot[q]; key = k2 > key ? k2 : key; slot[q] = 0ull; }
+        keys[r] = __uint_as_float(key_hi(key)) > 0.0f ? key : 0ull;   // (an IoU of 0 or NaN: nothing to force)
+    }
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    for (int it = 0; it < G; ++it) {
+        unsigned long long k = 0ull;
+        for (int r = threadIdx.x; r < G; r += kBipThreads) {   // largest IoU among the unassigned boxes, then the lowest box index
+            const unsigned hi = key_hi(keys[r]);
+            if (hi) { const unsigned long long c = make_key(hi, r); k = c > k ? c : k; }
+        }
+        k = bip_block_max(k, s_red);
+        if (key_hi(k) == 0u) break;   // (the same value in every thread) every anchor the remaining boxes overlap is taken
+        const int rs = key_col(k);
+        const unsigned long long kstar = keys[rs];
+        const int cs = key_col(kstar);
+        for (int r = threadIdx.x; r < G; r += kBipThreads) {
+            const unsigned long long kr = keys[r];
+            if (r != rs && key_hi(kr) && key_col(kr) == cs) rows[atomicAdd(&s_n, 1)] = r;
+        }
+        __syncthreads();
+        const int n = s_n;
+        if (threadIdx.x == 0) {
+            keys[rs] = 0ull;
+            s_taken[cs >> 5] |= 1u << (cs & 31);
+            gt_best[(size_t)(g0 + rs) * segs] = kstar;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_n = 0;   // (the next append is behind bip_block_max's barriers)
+        bip_rescan(rows, n, keys, s_part, [&](int r) {
+            const float* b = gt_rows + (size_t)(g0 + r) * gt_stride;
+            const float4 gb = make_float4(b[0], b[1], b[2], b[3]);
+            const float garea = area4(gb.x, gb.y, gb.z, gb.w);
+            unsigned bu = 0u;
+            int bi = 0;
+            for (int a = threadIdx.x; a < A; a += kBipThreads) {   // ascending anchors, strict >: the first maximum
+                const float4 c = to_corners(anchors[a]);
+                const float v = iou_corner(gb, garea, c, area4(c.x, c.y, c.z, c.w));
+                const bool taken = (s_taken[a >> 5] >> (a & 31)) & 1u;
+                const unsigned u = (!taken && v > 0.0f) ? __float_as_uint(v) : 0u;
+                if (u > bu) { bu = u; bi = a; }
+            }
+            return bu ? make_key(bu, bi) : 0ull;
+        });
+    }
+}
+
+// Matrix form: ONE workgroup plays the reference's loop on the working matrix `w` (the caller's for inplace, else a copy in the
+// workspace) literally -- G rounds, each zeroing a column and a row in memory -- so the matrix it leaves, and what exhaustion does
+// (every later round lands on flat index 0), are the reference's.  keys[r] is always the (ord(value), ~column) of row r's first maximum
+// in the CURRENT matrix, assigned (all-zero) rows included: zeroing column c can only matter to a row whose maximum sat in c (rescan)
+// or whose maximum is <= 0 (the new 0 at c may now be its first maximum).
+__global__ void __launch_bounds__(kBipThreads) match_bipartite_kernel(float* w, int G, int A, long long* __restrict__ anchor_idx,
+                                                                      int* __restrict__ num_matched, unsigned long long* keys, int* rows) {
+    __shared__ unsigned long long s_red[kBipWaves];
+    __shared__ unsigned long long s_part[kBipWaves][kBipWaves];
+    __shared__ int s_n;
+    auto sweep = [&](int r) {
+        const float* row = w + (size_t)r * A;
+        unsigned bu = 0u;
+        int bi = 0;
+        for (int a = threadIdx.x; a < A; a += kBipThreads) {
+            const unsigned u = ord_f32(row[a]);
+            if (u > bu) { bu = u; bi = a; }
+        }
+        return make_key(bu, bi);   // (a row of NaNs only: column 0)
+    };
+    for (int r = threadIdx.x; r < G; r += kBipThreads) anchor_idx[r] = -1;
+    if (threadIdx.x == 0) s_n = 0;
+    bip_rescan(nullptr, G, keys, s_part, sweep);
+    int matched = 0;
+    for (int it = 0; it < G; ++it) {
+        unsigned long long k = 0ull;
+        for (int r = threadIdx.x; r < G; r += kBipThreads) { const unsigned long long c = make_key(key_hi(keys[r]), r); k = c > k ? c : k; }
+        k = bip_block_max(k, s_red);   // the largest value, then the lowest row; its key holds the lowest column: the first flat index
+        const int rs = key_col(k);
+        const unsigned long long kstar = keys[rs];
+        const int cs = key_col(kstar);
+        for (int r = threadIdx.x; r < G; r += kBipThreads) {
+            if (r == rs) continue;
+            const unsigned long long kr = keys[r];
+            const int col = key_col(kr);
+            if (col == cs) { if (key_hi(kr) != kOrdZero) rows[atomicAdd(&s_n, 1)] = r; }   // (a maximum of 0 at cs stays where it is)
+            else if (kOrdZero > key_hi(kr) || (kOrdZero == key_hi(kr) && cs < col)) keys[r] = make_key(kOrdZero, cs);
+            w[(size_t)r * A + cs] = 0.0f;          // weights[:, idx % num_priors] = 0
+        }
+        for (int a = threadIdx.x; a < A; a += kBipThreads) w[(size_t)rs * A + a] = 0.0f;   // weights[idx // num_priors] = 0
+        __syncthreads();
+        const int n = s_n;
+        if (threadIdx.x == 0) {
+            keys[rs] = make_key(kOrdZero, 0);
+            anchor_idx[rs] = cs;
+            matched += key_hi(kstar) > kOrdZero;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_n = 0;
+        bip_rescan(rows, n, keys, s_part, sweep);
+    }
+    if (threadIdx.x == 0) *num_matched = matched;
+}
+
+__global__ void __launch_bounds__(256) copy_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
 }  // namespace ssdk
 
 using namespace ssdk;
@@ -257,6 +444,90 @@ extern "C" int ssdk_encode_ground_truth(const float* gt_rows, int gt_stride, con
     if (total_gt > 0) {
         hipLaunchKernelGGL(gt_argmax_kernel, dim3(total_gt, segs), dim3(kArgmaxThreads), 0, s, gt_rows, gt_stride, (const float4*)anchors, num_anchors, gt_best, gt_offsets, batch);
         SSDK_CHECK_LAUNCH("gt_argmax_kernel");
+    }
+    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
+    hipLaunchKernelGGL(assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
+                       num_anchors, matched_threshold, unmatched_threshold, gt_best, segs, target, box_idx);
+    SSDK_CHECK_LAUNCH("assign_kernel");
+    return SSDK_OK;
+}
+
+extern "C" size_t ssdk_match_bipartite_workspace_bytes(int num_boxes, int num_anchors) {
+    const size_t g = (size_t)(num_boxes > 0 ? num_boxes : 1), a = (size_t)(num_anchors > 0 ? num_anchors : 1);
+    Carver c(nullptr);
+    c.take<unsigned long long>(g);
+    c.take<int>(g);
+    c.take<float>(g * a);   // the working copy of a matrix that is not matched in place
+    return c.off;
+}
+
+extern "C" int ssdk_match_bipartite(float* weights, int num_boxes, int num_anchors, int inplace, int64_t* anchor_idx, int32_t* num_matched,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    SSDK_REQUIRE(num_boxes > 0 && num_anchors > 0, SSDK_E_INVALID, "ssdk_match_bipartite: boxes=%d anchors=%d", num_boxes, num_anchors);
+    SSDK_REQUIRE(weights && anchor_idx && num_matched, SSDK_E_INVALID, "ssdk_match_bipartite: null pointer");
+    SSDK_REQUIRE(num_boxes <= 65535, SSDK_E_INVALID, "ssdk_match_bipartite: more than 65535 boxes");
+    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_match_bipartite_workspace_bytes(num_boxes, num_anchors), SSDK_E_WORKSPACE,
+                 "ssdk_match_bipartite: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    Carver c(workspace);
+    unsigned long long* keys = c.take<unsigned long long>((size_t)num_boxes);
+    int* rows = c.take<int>((size_t)num_boxes);
+    float* w = weights;
+    if (!inplace) {
+        const size_t n = (size_t)num_boxes * (size_t)num_anchors;
+        w = c.take<float>(n);
+        const size_t want = (n + 255) / 256;
+        hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)(want > 2048 ? 2048 : want)), dim3(256), 0, s, weights, w, n);
+        SSDK_CHECK_LAUNCH("copy_f32_kernel");
+    }
+    hipLaunchKernelGGL(match_bipartite_kernel, dim3(1), dim3(kBipThreads), 0, s, w, num_boxes, num_anchors, (long long*)anchor_idx, num_matched, keys, rows);
+    SSDK_CHECK_LAUNCH("match_bipartite_kernel");
+    return SSDK_OK;
+}
+
+extern "C" size_t ssdk_encode_ground_truth_ex_workspace_bytes(int batch, int total_gt, int force_match) {
+    Carver c(nullptr);
+    c.off = ssdk_encode_ground_truth_workspace_bytes(batch, total_gt);
+    if (force_match == SSDK_FORCE_MATCH_BIPARTITE) {
+        c.take<unsigned long long>((size_t)(total_gt > 0 ? total_gt : 1));
+        c.take<int>((size_t)(total_gt > 0 ? total_gt : 1));
+    }
+    return c.off;
+}
+
+extern "C" int ssdk_encode_ground_truth_ex(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                           const float* anchors, int num_anchors, float matched_threshold, float unmatched_threshold,
+                                           int force_match, float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+    SSDK_REQUIRE(force_match == SSDK_FORCE_MATCH_PER_PREDICTION || force_match == SSDK_FORCE_MATCH_BIPARTITE, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_ex: force_match=%d", force_match);
+    if (force_match == SSDK_FORCE_MATCH_PER_PREDICTION)
+        return ssdk_encode_ground_truth(gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, matched_threshold,
+                                        unmatched_threshold, target, box_idx, workspace, workspace_bytes, stream);
+    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_ex: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
+    SSDK_REQUIRE(batch <= 65535 && total_gt <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_ex: batch/total_gt exceed grid limits");
+    SSDK_REQUIRE(num_anchors <= kBipMaxAnchors, SSDK_E_UNSUPPORTED, "ssdk_encode_ground_truth_ex: bipartite matching takes at most %d anchors, got %d",
+                 kBipMaxAnchors, num_anchors);
+    SSDK_REQUIRE(gt_offsets && anchors && target && (gt_rows || total_gt == 0), SSDK_E_INVALID, "ssdk_encode_ground_truth_ex: null pointer");
+    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_ex: gt_stride=%d < 6", gt_stride);
+    SSDK_REQUIRE(matched_threshold >= unmatched_threshold, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_ex: matched_threshold < unmatched_threshold (matcher.py:43)");
+    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_ex_workspace_bytes(batch, total_gt, force_match), SSDK_E_WORKSPACE,
+                 "ssdk_encode_ground_truth_ex: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t slots = (size_t)(total_gt > 0 ? total_gt : 1);
+    Carver c(workspace);
+    unsigned long long* gt_best = c.take<unsigned long long>(slots * kArgmaxMaxSegs);
+    unsigned long long* spill_keys = c.take<unsigned long long>(slots);
+    int* spill_rows = c.take<int>(slots);
+    const int segs = argmax_segs(num_anchors);
+    if (total_gt > 0) {
+        hipLaunchKernelGGL(gt_argmax_kernel, dim3(total_gt, segs), dim3(kArgmaxThreads), 0, s, gt_rows, gt_stride, (const float4*)anchors, num_anchors, gt_best, gt_offsets, batch);
+        SSDK_CHECK_LAUNCH("gt_argmax_kernel");
+        hipLaunchKernelGGL(bipartite_resolve_kernel, dim3(batch), dim3(kBipThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors,
+                           gt_best, segs, spill_keys, spill_rows);
+        SSDK_CHECK_LAUNCH("bipartite_resolve_kernel");
     }
     dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
     hipLaunchKernelGGL(assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,

@@ -1,7 +1,8 @@
 """detection/matcher.py.  In the training path the matcher (match_per_prediction, matcher.py:33-56) is fused with the IoU into
 ``ssdk_encode_ground_truth`` (csrc/match.hip) and no [Boxes, AnchorBoxes] matrix exists; ``match_per_prediction`` below is the
 reference's own function on a given weight matrix (``ssdk_match_per_prediction``), ``match_boxes`` the fused form for one box set.
-``match_bipartite`` (matcher.py:7-31) is not called by anything in the reference and is not reproduced."""
+``match_bipartite`` (matcher.py:7-31) is the reference's own function on a given matrix too (``ssdk_match_bipartite``); nothing in the
+reference calls it, here it is also the opt-in force stage of the fused path (``TargetAssigner(force_match='bipartite')``)."""
 import torch
 
 from .. import _lib
@@ -10,15 +11,48 @@ NOT_MATCHED = -2  # matcher.py:4
 IGNORE = -1       # matcher.py:5
 
 
-def match_boxes(gt_boxes, anchors, matched_threshold, unmatched_threshold=None):
+def match_bipartite(weights, inplace=False):
+    """
+    Args:
+        weights: torch.tensor(:shape [Boxes, AnchorBoxes]) fp32 on the GPU
+    Returns:
+        box_idx: torch.tensor(:shape [Boxes]) int64
+        anchor_idx: torch.tensor(:shape [Boxes]) int64 -- matcher.py:7-31: Boxes times, the argmax of the whole matrix (first flat index
+        on ties) gives that row that column, then the column and the row are zeroed.
+
+    Exhaustion (two boxes whose only positive entry is the same column, or Boxes > AnchorBoxes): once the maximum is 0 the reference's
+    argmax is flat index 0 in every later round, so ``anchor_idx[0] == 0`` whenever a box was left over, as there; the left-over boxes'
+    entries, which the reference leaves as ``torch.empty`` made them, are -1 here.  ``inplace=True`` (fp32 contiguous ``weights``)
+    leaves ``weights`` as the reference leaves it; otherwise it is untouched.  The reference's assert (a row without a positive entry,
+    a NaN maximum included) raises AssertionError here too and costs one sync, as there.
+    """
+    _lib.require_cuda(weights)
+    if weights.dim() != 2 or weights.size(0) == 0 or weights.size(1) == 0:
+        raise ValueError('weights must be [Boxes, AnchorBoxes] with at least one box and one anchor')
+    assert weights.max(dim=1)[0].gt(0).all().item()   # matcher.py:15
+    if inplace and not (weights.dtype == torch.float32 and weights.is_contiguous()):
+        raise ValueError('match_bipartite(inplace=True) takes a contiguous fp32 matrix')
+    lib = _lib.lib()
+    w = weights if inplace else weights.float().contiguous()
+    G, A = w.shape
+    anchor_idx = torch.empty((G,), dtype=torch.int64, device=w.device)
+    num_matched = torch.empty((1,), dtype=torch.int32, device=w.device)
+    ws = _lib.scratch(lib.ssdk_match_bipartite_workspace_bytes(G, A), w.device, 'match_bipartite')
+    _lib.check(lib.ssdk_match_bipartite(_lib.ptr(w), G, A, int(bool(inplace)), _lib.ptr(anchor_idx), _lib.ptr(num_matched), _lib.ptr(ws),
+                                        ws.numel(), _lib.current_stream()), 'ssdk_match_bipartite')
+    return torch.arange(G, dtype=torch.int64, device=w.device), anchor_idx
+
+
+def match_boxes(gt_boxes, anchors, matched_threshold, unmatched_threshold=None, force_match='per_prediction'):
     """box_idx int64 [A] for one image: IoU (box_utils.py:83-101) + match_per_prediction (matcher.py:33-56,
-    force_match_for_each_target=True) on the GPU.  ``gt_boxes`` [G, >=4] corner form, ``anchors`` [A,4] centroid."""
+    force_match_for_each_target=True) on the GPU.  ``gt_boxes`` [G, >=4] corner form, ``anchors`` [A,4] centroid.
+    ``force_match='bipartite'``: the force stage is match_bipartite's (see ``TargetAssigner``)."""
     from .target_assigner import TargetAssigner
     if unmatched_threshold is None:
         unmatched_threshold = matched_threshold
     gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
     gt[:, :4] = gt_boxes[:, :4]
-    _, idx = TargetAssigner(matched_threshold, unmatched_threshold).encode_ground_truth([gt], anchors, return_box_idx=True)
+    _, idx = TargetAssigner(matched_threshold, unmatched_threshold, force_match).encode_ground_truth([gt], anchors, return_box_idx=True)
     return idx[0].long()
 
 

@@ -81,10 +81,23 @@ def pack_ground_truth(ground_truth, device, row=GT_ROW):
     return rows.contiguous(), offs, total
 
 
+FORCE_MATCH = {'per_prediction': 0, 'bipartite': 1}   # SSDK_FORCE_MATCH_* (include/ssdk.h)
+
+
 class TargetAssigner(object):
-    def __init__(self, matched_threshold, unmatched_threshold):
+    """``force_match`` (not in the reference; default ``'per_prediction'`` = the reference's rule): how every ground-truth box is given
+    an anchor regardless of the thresholds.  ``'per_prediction'``: each box's best anchor, the highest box index winning an anchor that
+    several boxes share (matcher.py:52-54) -- the boxes that lose it may end up with no positive anchor at all.  ``'bipartite'``: the
+    threshold stage is ``match_per_prediction(..., force_match_for_each_target=False)``, then ``box_idx[anchor_idx] = box_idx_b`` with
+    ``match_bipartite``'s greedy matching (matcher.py:7-31) -- every box an anchor of its own.  Unlike ``matcher.match_bipartite``, the
+    fused stage stops once no remaining box overlaps a free anchor: those boxes get no forced anchor and box 0 keeps its own."""
+
+    def __init__(self, matched_threshold, unmatched_threshold, force_match='per_prediction'):
+        if force_match not in FORCE_MATCH:
+            raise ValueError(f'TargetAssigner: force_match={force_match!r}, expected one of {sorted(FORCE_MATCH)}')
         self.matched_threshold = matched_threshold
         self.unmatched_threshold = unmatched_threshold
+        self.force_match = force_match
         self._ws = None
 
     def encode_ground_truth(self, ground_truth, anchors, return_box_idx=False):
@@ -109,14 +122,23 @@ class TargetAssigner(object):
             rows, offs, total = pack_ground_truth(ground_truth, device)
         target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
         box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
-        need = lib.ssdk_encode_ground_truth_workspace_bytes(batch_size, total)
+        mode = FORCE_MATCH[self.force_match]
+        need = lib.ssdk_encode_ground_truth_ex_workspace_bytes(batch_size, total, mode) if mode else \
+            lib.ssdk_encode_ground_truth_workspace_bytes(batch_size, total)
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:
             self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
-        _lib.check(lib.ssdk_encode_ground_truth(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total,
-                                                _lib.ptr(anchors), num_anchors, float(self.matched_threshold),
-                                                float(self.unmatched_threshold), _lib.ptr(target), _lib.ptr(box_idx),
-                                                _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
-                   'ssdk_encode_ground_truth')
+        if mode:
+            _lib.check(lib.ssdk_encode_ground_truth_ex(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total,
+                                                       _lib.ptr(anchors), num_anchors, float(self.matched_threshold),
+                                                       float(self.unmatched_threshold), mode, _lib.ptr(target), _lib.ptr(box_idx),
+                                                       _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
+                       'ssdk_encode_ground_truth_ex')
+        else:   # the default: the entry point and the kernels it always had
+            _lib.check(lib.ssdk_encode_ground_truth(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total,
+                                                    _lib.ptr(anchors), num_anchors, float(self.matched_threshold),
+                                                    float(self.unmatched_threshold), _lib.ptr(target), _lib.ptr(box_idx),
+                                                    _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
+                       'ssdk_encode_ground_truth')
         # keep the staging tensors alive until the stream has consumed them
         target._ssdk_keepalive = (rows, offs)
         return (target, box_idx) if return_box_idx else target
