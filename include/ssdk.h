@@ -362,7 +362,10 @@ typedef struct ssdk_head_level {
  * left to the library between calls (it holds parked partial tiles and their ready flags, told apart from call to call by a launch
  * counter).  With it, a launch of a few rounds of whole tiles runs in stream-K form: the K slices of the whole launch are cut into equal
  * ranges, one per resident workgroup, and a tile that straddles two ranges is summed through the workspace -- same results up to fp32
- * summation order of that one K split. */
+ * summation order of that one K split.  The last 256-byte-rounded part of the workspace is its flag region: 512 ready flags (back to 0
+ * once their partial tile was consumed), the timeout counter, and the launch counter of the last stream-K launch that ran on it
+ * (a launch that took another form leaves the region as it was).  That word is DIAGNOSTIC only -- tests and fault analysis read it; the
+ * library never does, and no caller may build on it. */
 /* The stream-K fix-up wait is bounded (a workgroup that never runs must not hang the GPU), and a wait that runs out is LOUD: the owner fills
  * its output tile with NaN instead of storing an incomplete sum, counts the event in the workspace, and sets a sticky word in pinned host
  * memory that makes this and every later ssdk_heads_fwd of the process return SSDK_E_STREAMK_TIMEOUT.  ssdk_heads_fwd_timeouts reads the

@@ -911,6 +911,9 @@ __global__ void __launch_bounds__(kConvThreads, SSDK_CONV_WAVES) igemm_streamk_k
     // ssdk_heads_fwd's host-side check, so the kernel itself refuses to produce numbers from then on
     const bool poisoned = __hip_atomic_load(sk.timeouts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
     const bool drop = g_sk_drop_wg == s;
+    // the word behind the timeout counter: the launch counter of the last stream-K launch on this workspace.  Consumed flags go back to 0
+    // (dma_tile), so this is what a healthy launch leaves behind in the flag region: "the stream-K form ran here" (tests, diagnosis)
+    if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(sk.timeouts + 1, sk.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     while (u < u_end) {
         locate(u, pi, m_tile, n_block, slice, tn);
         const ConvProblem& g = grp.p[pi];
@@ -2956,7 +2959,8 @@ static void narrow_for_atomics(ConvProblem& g) {
 constexpr int kStreamKWgs = 512;   // two 64 KB-LDS workgroups per CU x 256 CUs: the most a stream-K launch uses, and the size its workspace is laid out for
 struct StreamKWs {
     float* partial;
-    unsigned* flags;   // [kStreamKWgs + 2]: a flag per workgroup, then the timeout counter at [kStreamKWgs] (a FIXED place: a launch capped
+    unsigned* flags;   // [kStreamKWgs + 2]: a flag per workgroup (back to 0 once consumed), then the timeout counter at [kStreamKWgs] and the launch
+                       // counter of the last stream-K launch at [kStreamKWgs + 1] (FIXED places: a launch capped
                        // below kStreamKWgs workgroups -- ssdk_heads_fwd_ex -- shares the workspace with uncapped ones)
     int nwg;
 };
