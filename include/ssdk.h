@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 117
+#define SSDK_VERSION 118
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -583,6 +583,17 @@ int ssdk_upsample_nearest_add_fwd(const float* fine, const float* coarse, int ba
 /* gradient w.r.t. coarse: each coarse pixel sums dout over the fine pixels it was copied to (the gradient w.r.t. fine is dout). */
 int ssdk_upsample_nearest_add_bwd(const float* dout, int batch, int hf, int wf, int hc, int wc, int channels,
                                   float* dcoarse, void* stream);
+/* bf/modules/features.py:107-108, :264-265 with interpolation_mode='bilinear': out = fine + F.interpolate(coarse, size=(hf, wf),
+ * mode='bilinear') (align_corners=False, no antialiasing); fine == NULL: plain bilinear resizing (features.py:371-373, M2Det base
+ * features).  Per axis src = max(in / out * (dst + 0.5) - 0.5, 0), i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1), l1 = src - i0,
+ * l0 = 1 - l1; out = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11).  Any pair of sizes (up, equal = identity, down, 1). */
+int ssdk_upsample_bilinear_add_fwd(const float* fine, const float* coarse, int batch, int hf, int wf, int hc, int wc,
+                                   int channels, float* out, void* stream);
+/* gradient w.r.t. coarse (torch's upsample_bilinear2d_backward; the gradient w.r.t. fine is dout): each coarse pixel gathers weight * dout
+ * over the fine pixels that read it, with the forward's own weights, rows and columns in ascending order -- no atomics, no zero-fill,
+ * every element of dcoarse written: deterministic in both modes. */
+int ssdk_upsample_bilinear_add_bwd(const float* dout, int batch, int hf, int wf, int hc, int wc, int channels,
+                                   float* dcoarse, void* stream);
 
 /* ---- M2Det scale-wise feature aggregation (next-row f1), bf/modules/features.py:273-300 ----------------------------- */
 

@@ -67,8 +67,9 @@ class FeaturePyramid(Features):
     """FPN neck -- restatement of bf/modules/features.py:52-120 (ref. arXiv:1612.03144), SURVEY.md §8f1.
 
     Lateral 1x1 convs and the 3x3 output blocks run on libssdk's implicit-GEMM kernels (``ops.conv2d`` / ``Conv2dBn``), the
-    top-down ``features[i] += interpolate(features[i+1], nearest)`` on ``ssdk_upsample_nearest_add``.  Module names
-    (``pyramid_lateral``, ``pyramid_output``) follow the reference so checkpoints map 1:1."""
+    top-down ``features[i] += interpolate(features[i+1], interpolation_mode)`` on ``ssdk_upsample_nearest_add`` /
+    ``ssdk_upsample_bilinear_add`` ('nearest' and 'bilinear' are on libssdk; any other mode is torch's interpolation, said once).  Module
+    names (``pyramid_lateral``, ``pyramid_output``) follow the reference so checkpoints map 1:1."""
 
     def __init__(self, base, out_layers, pyramid_layers, pyramid_channels, interpolation_mode='nearest', use_depthwise=False,
                  activation={'name': 'ReLU', 'args': {'inplace': True}}, initializer={'name': 'xavier_normal_'}, **kwargs):
@@ -114,12 +115,20 @@ class FeaturePyramid(Features):
 
 def _upsample_add(fine, coarse, mode):
     """fine + F.interpolate(coarse, size of fine, mode) (features.py:107-108, :264-265).  'nearest' -- the default and what every sample
-    config uses -- is the libssdk kernel; any other mode is torch's own interpolation (the neck is PyTorch-ROCm territory, SURVEY.md 2
-    row 16), said once."""
-    if mode == 'nearest':
-        return ops.upsample_add(fine, coarse)
+    config uses -- and 'bilinear' are libssdk kernels (one launch, no upsampled map); any other mode is torch's own interpolation (the
+    neck is PyTorch-ROCm territory), said once."""
+    if mode in ops.UPSAMPLE_MODES:
+        return ops.upsample_add(fine, coarse, mode)
     conv._warn_stock('interpolate', f"interpolation_mode={mode!r}")
     return fine + F.interpolate(coarse, size=fine.shape[2:], mode=mode)
+
+
+def _upsample(x, size, mode):
+    """F.interpolate(x, size, mode) (features.py:371-373), on libssdk for the modes of _upsample_add."""
+    if mode in ops.UPSAMPLE_MODES:
+        return ops.upsample(x, size, mode)
+    conv._warn_stock('interpolate', f"interpolation_mode={mode!r}")
+    return F.interpolate(x, size=size, mode=mode)
 
 
 class DepthwiseFeaturePyramid(Features):
@@ -236,7 +245,8 @@ def update_existing(dict1, dict2):
 
 class ThinnedUshapeModule(nn.Module):
     """M2Det TUM -- restatement of bf/modules/features.py:215-270 (encoder of stride-2 3x3 blocks, decoder of 1x1 blocks with
-    nearest upsample + skip add, 1x1 smoothing of every decoder stage).  Conv2dBn blocks and the upsample-add run on libssdk."""
+    upsample + skip add, 1x1 smoothing of every decoder stage).  Conv2dBn blocks and the upsample-add run on libssdk
+    (``interpolation_mode`` 'nearest' or 'bilinear'; any other mode is torch's interpolation, said once)."""
 
     def __init__(self, in_channels, inner_channels, out_channels, num_scales, interpolation_mode='nearest', use_depthwise=False,
                  activation={'name': 'ReLU', 'args': {'inplace': True}}, initializer={'name': 'xavier_normal_'}):
@@ -309,7 +319,8 @@ class ScalewiseFeatureAggregationModule(nn.Module):
 
 
 class MultilevelFeaturePyramid(Features):
-    """M2Det MLFPN neck -- restatement of bf/modules/features.py:303-393."""
+    """M2Det MLFPN neck -- restatement of bf/modules/features.py:303-393.  ``interpolation_mode`` ('nearest' or 'bilinear' on libssdk)
+    governs the TUMs' top-down steps AND the upscaling of the base features (features.py:371-373)."""
 
     def __init__(self, base, out_layers, num_scales, num_tums, base_reduced_channels=[256, 512], reduced_channels=128,
                  interpolation_mode='nearest', use_depthwise=False, activation={'name': 'ReLU', 'args': {'inplace': True}},
@@ -356,7 +367,7 @@ class MultilevelFeaturePyramid(Features):
                 ops.prepare_weight_transposes(group)
         base_reduced = [reducer(source) for reducer, source in zip(self.base_reducers, sources)]
         size = base_reduced[0].shape[2:]
-        upscaled = [base_reduced[0]] + [ops.upsample_nearest(f, size) for f in base_reduced[1:]]   # features.py:369-371
+        upscaled = [base_reduced[0]] + [_upsample(f, size, self.interpolation_mode) for f in base_reduced[1:]]   # features.py:371-373
         base_features = torch.cat(upscaled, dim=1)
         features = [[f] for f in self.tums[0](base_features)]
         reduced_all = self._reducers_merged(base_features)

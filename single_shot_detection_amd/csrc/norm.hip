@@ -560,6 +560,126 @@ extern "C" int ssdk_upsample_nearest_add_bwd(const float* dout, int batch, int h
     return SSDK_OK;
 }
 
+// ---- the same step in bilinear mode: out = [fine +] bilinear_upsample(coarse) ----------------------------------------
+// Reference: bf/modules/features.py:107-108, :264-265, :371-373 with interpolation_mode='bilinear', which F.interpolate runs with
+// align_corners=False.  Per axis: src = max(in / out * (dst + 0.5) - 0.5, 0), i0 = min((int)src, in - 1), i1 = i0 + (i0 < in - 1),
+// l1 = clamp(src - i0, 0, 1), l0 = 1 - l1; out = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11).  Any pair of sizes: upscaling,
+// equal sizes (l1 == 0: the identity), downscaling (still two taps per axis, no antialiasing), in == 1 (i0 == i1 == 0).
+namespace ssdk {
+struct BilinearTap {
+    int i0, i1;
+    float l0, l1;
+};
+
+// The taps of output index `dst` along one axis.  The ONLY place they are computed: the backward kernel calls it for every candidate pixel,
+// so it is the adjoint of the forward as computed, bit for bit, not of a second derivation.  (The explicit fused multiply-add keeps the
+// compiler from contracting the two inlined copies differently.)
+__device__ __forceinline__ BilinearTap bilinear_tap(int dst, float scale, int in) {
+    const float src = fmaxf(__fmaf_rn(scale, (float)dst + 0.5f, -0.5f), 0.f);
+    BilinearTap t;
+    t.i0 = min((int)src, in - 1);
+    t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
+    t.l1 = fminf(fmaxf(src - (float)t.i0, 0.f), 1.f);
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+
+__global__ void __launch_bounds__(256) upsample_bilinear_add_kernel(const float4* __restrict__ fine, const float4* __restrict__ coarse, int B,
+                                                                    int Hf, int Wf, int Hc, int Wc, int C4, float4* __restrict__ out) {
+    const long long total = (long long)B * Hf * Wf * C4;
+    const float sh = (float)Hc / (float)Hf, sw = (float)Wc / (float)Wf;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C4);
+        long long p = i / C4;
+        const int x = (int)(p % Wf); p /= Wf;
+        const int y = (int)(p % Hf);
+        const int b = (int)(p / Hf);
+        const BilinearTap ty = bilinear_tap(y, sh, Hc), tx = bilinear_tap(x, sw, Wc);
+        const float4* r0 = coarse + ((long long)b * Hc + ty.i0) * Wc * C4 + c;
+        const float4* r1 = coarse + ((long long)b * Hc + ty.i1) * Wc * C4 + c;
+        const float4 v00 = r0[(long long)tx.i0 * C4], v01 = r0[(long long)tx.i1 * C4];
+        const float4 v10 = r1[(long long)tx.i0 * C4], v11 = r1[(long long)tx.i1 * C4];
+        float4 u;
+        u.x = ty.l0 * (tx.l0 * v00.x + tx.l1 * v01.x) + ty.l1 * (tx.l0 * v10.x + tx.l1 * v11.x);
+        u.y = ty.l0 * (tx.l0 * v00.y + tx.l1 * v01.y) + ty.l1 * (tx.l0 * v10.y + tx.l1 * v11.y);
+        u.z = ty.l0 * (tx.l0 * v00.z + tx.l1 * v01.z) + ty.l1 * (tx.l0 * v10.z + tx.l1 * v11.z);
+        u.w = ty.l0 * (tx.l0 * v00.w + tx.l1 * v01.w) + ty.l1 * (tx.l0 * v10.w + tx.l1 * v11.w);
+        if (fine) {
+            const float4 a = fine[i];
+            u = make_float4(a.x + u.x, a.y + u.y, a.z + u.z, a.w + u.w);
+        }
+        out[i] = u;
+    }
+}
+
+// First and last candidate output index that can have a tap at input index `c`: i0 == c or i1 == c needs src in (c - 1, c + 1), i.e.
+// dst in ((c - 0.5) / scale - 0.5, (c + 1.5) / scale - 0.5); the clamp of src at 0 only moves pixels onto c == 0, whose window starts at 0
+// anyway.  Widened by 2 on either side: the fp32 window and the fp32 src are each off by less than out * 2^-21, far below 1 for any map.
+// Every candidate's taps are recomputed and tested, so a wide window costs time, never correctness.  Empty (lo > hi) when downscaling skips
+// the index.
+__device__ __forceinline__ void bilinear_window(int c, float scale, int out, int& lo, int& hi) {
+    lo = max(0, (int)floorf(((float)c - 0.5f) / scale - 0.5f) - 2);
+    hi = min(out - 1, (int)ceilf(((float)c + 1.5f) / scale - 0.5f) + 2);
+}
+
+// dcoarse[yc][xc] = sum over the fine pixels with a tap at (yc, xc) of (row weight) * (column weight) * dout -- Wy^T . G . Wx in gather
+// form: rows and columns in ascending order, no atomics, every element written (zeros where the window is empty): deterministic.
+__global__ void __launch_bounds__(256) upsample_bilinear_add_bwd_kernel(const float4* __restrict__ dout, int B, int Hf, int Wf, int Hc, int Wc,
+                                                                        int C4, float4* __restrict__ dcoarse) {
+    const long long total = (long long)B * Hc * Wc * C4;
+    const float sh = (float)Hc / (float)Hf, sw = (float)Wc / (float)Wf;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C4);
+        long long p = i / C4;
+        const int xc = (int)(p % Wc); p /= Wc;
+        const int yc = (int)(p % Hc);
+        const int b = (int)(p / Hc);
+        int y0, y1, x0, x1;
+        bilinear_window(yc, sh, Hf, y0, y1);
+        bilinear_window(xc, sw, Wf, x0, x1);
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int y = y0; y <= y1; ++y) {
+            const BilinearTap ty = bilinear_tap(y, sh, Hc);
+            if (ty.i0 != yc && ty.i1 != yc) continue;
+            const float wy = (ty.i0 == yc ? ty.l0 : 0.f) + (ty.i1 == yc ? ty.l1 : 0.f);   // (both at the far edge and when Hc == 1)
+            const float4* row = dout + ((long long)b * Hf + y) * Wf * C4 + c;
+            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int x = x0; x <= x1; ++x) {
+                const BilinearTap tx = bilinear_tap(x, sw, Wc);
+                if (tx.i0 != xc && tx.i1 != xc) continue;
+                const float wx = (tx.i0 == xc ? tx.l0 : 0.f) + (tx.i1 == xc ? tx.l1 : 0.f);
+                const float4 g = row[(long long)x * C4];
+                r.x += wx * g.x; r.y += wx * g.y; r.z += wx * g.z; r.w += wx * g.w;
+            }
+            s.x += wy * r.x; s.y += wy * r.y; s.z += wy * r.z; s.w += wy * r.w;
+        }
+        dcoarse[i] = s;
+    }
+}
+}  // namespace ssdk
+
+extern "C" int ssdk_upsample_bilinear_add_fwd(const float* fine, const float* coarse, int batch, int hf, int wf, int hc, int wc, int channels,
+                                              float* out, void* stream) {
+    SSDK_REQUIRE(coarse && out && batch > 0 && hf > 0 && wf > 0 && hc > 0 && wc > 0 && channels > 0 && channels % 4 == 0, SSDK_E_INVALID,
+                 "ssdk_upsample_bilinear_add_fwd: bad arguments (channels %% 4 == 0)");
+    const long long n4 = (long long)batch * hf * wf * channels / 4;
+    hipLaunchKernelGGL(upsample_bilinear_add_kernel, dim3(stream_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)fine,
+                       (const float4*)coarse, batch, hf, wf, hc, wc, channels / 4, (float4*)out);
+    SSDK_CHECK_LAUNCH("upsample_bilinear_add_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_upsample_bilinear_add_bwd(const float* dout, int batch, int hf, int wf, int hc, int wc, int channels, float* dcoarse,
+                                              void* stream) {
+    SSDK_REQUIRE(dout && dcoarse && batch > 0 && hf > 0 && wf > 0 && hc > 0 && wc > 0 && channels > 0 && channels % 4 == 0, SSDK_E_INVALID,
+                 "ssdk_upsample_bilinear_add_bwd: bad arguments (channels %% 4 == 0)");
+    const long long n4 = (long long)batch * hc * wc * channels / 4;
+    hipLaunchKernelGGL(upsample_bilinear_add_bwd_kernel, dim3(stream_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)dout,
+                       batch, hf, wf, hc, wc, channels / 4, (float4*)dcoarse);
+    SSDK_CHECK_LAUNCH("upsample_bilinear_add_bwd_kernel");
+    return SSDK_OK;
+}
+
 
 // ---- SFAM (M2Det scale-wise feature aggregation): squeeze-excite gate ---------------------------------
 // Reference: bf/modules/features.py:286-298  x = adaptive_avg_pool2d(f, 1); x = fc2(relu(fc1(x))); out = f * sigmoid(x).

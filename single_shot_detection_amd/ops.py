@@ -792,19 +792,30 @@ def batch_norm_levels(xs, bns, relu=False):
     return [batch_norm(x, bn, relu) for x, bn in zip(xs, bns)]
 
 
+UPSAMPLE_MODES = ('nearest', 'bilinear')   # the interpolation modes on libssdk: ssdk_upsample_<mode>_add_fwd / _bwd
+
+
+def _upsample_entry(mode, direction):
+    if mode not in UPSAMPLE_MODES:
+        raise ValueError(f"upsampling mode {mode!r} is not on libssdk: the modes are 'nearest' and 'bilinear'")
+    name = f'ssdk_upsample_{mode}_add_{direction}'
+    return getattr(_lib.lib(), name), name
+
+
 class _UpsampleAddFn(torch.autograd.Function):
-    """out = fine + nearest_upsample(coarse, size of fine)   (FPN top-down step, bf/modules/features.py:106-107)"""
+    """out = fine + F.interpolate(coarse, size of fine, mode)   (FPN top-down step, bf/modules/features.py:106-108; TUM, :263-265)"""
 
     @staticmethod
-    def forward(ctx, fine, coarse):
+    def forward(ctx, fine, coarse, mode):
+        fwd, name = _upsample_entry(mode, 'fwd')
         _lib.require_cuda(fine, coarse)
         fine, coarse = _nhwc(fine), _nhwc(coarse)
         B, C, Hf, Wf = fine.shape
         assert coarse.shape[0] == B and coarse.shape[1] == C
         out = torch.empty_like(fine, memory_format=torch.channels_last)
-        _lib.check(_lib.lib().ssdk_upsample_nearest_add_fwd(_dp(fine), _dp(coarse), B, Hf, Wf, coarse.shape[2], coarse.shape[3], C, _dp(out),
-                                                            _lib.current_stream()), 'ssdk_upsample_nearest_add_fwd')
+        _lib.check(fwd(_dp(fine), _dp(coarse), B, Hf, Wf, coarse.shape[2], coarse.shape[3], C, _dp(out), _lib.current_stream()), name)
         ctx.shapes = (B, C, Hf, Wf, coarse.shape[2], coarse.shape[3])
+        ctx.mode = mode
         return out
 
     @staticmethod
@@ -813,42 +824,50 @@ class _UpsampleAddFn(torch.autograd.Function):
         dout = _nhwc(dout)
         dcoarse = None
         if ctx.needs_input_grad[1]:
+            bwd, name = _upsample_entry(ctx.mode, 'bwd')
             dcoarse = torch.empty((B, C, Hc, Wc), dtype=torch.float32, device=dout.device, memory_format=torch.channels_last)
-            _lib.check(_lib.lib().ssdk_upsample_nearest_add_bwd(_dp(dout), B, Hf, Wf, Hc, Wc, C, _dp(dcoarse), _lib.current_stream()),
-                       'ssdk_upsample_nearest_add_bwd')
-        return (dout if ctx.needs_input_grad[0] else None), dcoarse
+            _lib.check(bwd(_dp(dout), B, Hf, Wf, Hc, Wc, C, _dp(dcoarse), _lib.current_stream()), name)
+        return (dout if ctx.needs_input_grad[0] else None), dcoarse, None
 
 
-def upsample_add(fine, coarse):
-    return _UpsampleAddFn.apply(fine, coarse)
+def upsample_add(fine, coarse, mode='nearest'):
+    """fine + F.interpolate(coarse, size=fine.shape[2:], mode=mode) in one launch; ``mode`` is 'nearest' or 'bilinear' (align_corners=False,
+    as F.interpolate runs it).  The backward passes dout through to ``fine`` and gathers ``dcoarse`` without atomics in either mode."""
+    return _UpsampleAddFn.apply(fine, coarse, mode)
 
 
 class _UpsampleFn(torch.autograd.Function):
-    """F.interpolate(x, size=(h, w), mode='nearest') (bf/modules/features.py:371)."""
+    """F.interpolate(x, size=(h, w), mode=mode) (bf/modules/features.py:371-373)."""
 
     @staticmethod
-    def forward(ctx, coarse, hf, wf):
+    def forward(ctx, coarse, hf, wf, mode):
+        fwd, name = _upsample_entry(mode, 'fwd')
         _lib.require_cuda(coarse)
         coarse = _nhwc(coarse)
         B, C, Hc, Wc = coarse.shape
         out = torch.empty((B, C, hf, wf), dtype=torch.float32, device=coarse.device, memory_format=torch.channels_last)
-        _lib.check(_lib.lib().ssdk_upsample_nearest_add_fwd(None, _dp(coarse), B, hf, wf, Hc, Wc, C, _dp(out), _lib.current_stream()),
-                   'ssdk_upsample_nearest_add_fwd')
+        _lib.check(fwd(None, _dp(coarse), B, hf, wf, Hc, Wc, C, _dp(out), _lib.current_stream()), name)
         ctx.shapes = (B, C, hf, wf, Hc, Wc)
+        ctx.mode = mode
         return out
 
     @staticmethod
     def backward(ctx, dout):
         B, C, Hf, Wf, Hc, Wc = ctx.shapes
+        bwd, name = _upsample_entry(ctx.mode, 'bwd')
         dout = _nhwc(dout)
         dcoarse = torch.empty((B, C, Hc, Wc), dtype=torch.float32, device=dout.device, memory_format=torch.channels_last)
-        _lib.check(_lib.lib().ssdk_upsample_nearest_add_bwd(_dp(dout), B, Hf, Wf, Hc, Wc, C, _dp(dcoarse), _lib.current_stream()),
-                   'ssdk_upsample_nearest_add_bwd')
-        return dcoarse, None, None
+        _lib.check(bwd(_dp(dout), B, Hf, Wf, Hc, Wc, C, _dp(dcoarse), _lib.current_stream()), name)
+        return dcoarse, None, None, None
+
+
+def upsample(x, size, mode='nearest'):
+    """F.interpolate(x, size=size, mode=mode) for the modes of ``upsample_add``."""
+    return _UpsampleFn.apply(x, int(size[0]), int(size[1]), mode)
 
 
 def upsample_nearest(x, size):
-    return _UpsampleFn.apply(x, int(size[0]), int(size[1]))
+    return upsample(x, size, 'nearest')
 
 
 class _AvgPoolFn(torch.autograd.Function):
