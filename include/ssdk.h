@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 118
+#define SSDK_VERSION 119
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -631,6 +631,30 @@ int ssdk_depthwise_conv2d_fwd(const float* x, const float* w, const float* bias,
                               int stride, int pad, float* y, void* stream);
 int ssdk_depthwise_conv2d_bwd(const float* x, const float* w, const float* dy, int batch, int hin, int win, int channels, int ksize,
                               int stride, int pad, float* dx, float* dw, float* db, int accumulate, void* stream);
+
+/* The same stencil over 1 <= n_levels <= 8 maps that share batch, channels (% 4), weight [channels][k*k] and bias but have their own
+ * hs[l] x ws[l]: the RetinaNet-lite tower of SharedConvPredictor(use_depthwise=True) (detection/modules/predictors.py:33-35,67-68), whose
+ * DepthwiseConv2dBn (bf/modules/conv.py:72-76) is shared by the pyramid levels.  xs / ys / dys / dxs are HOST arrays of n_levels device
+ * pointers (16-byte aligned NHWC fp32 maps); they are packed into the kernel argument, so there is no device-side table, no allocation
+ * and no synchronisation (safe inside a captured graph).  Every level is checked by the rules of ssdk_depthwise_conv2d_* before any
+ * launch; a refusal (< 0) names the function and the level.
+ *   fwd: one launch; every level's y equals ssdk_depthwise_conv2d_fwd's bit for bit (the same tap order and fmaf chain).
+ *   bwd: dx (one launch over the levels with a non-NULL dxs entry; dxs itself may be NULL) equals ssdk_depthwise_conv2d_bwd's bit for
+ *        bit.  dw [channels][k*k] and db (either may be NULL) are OVERWRITTEN by two launches without atomics or zero-fill: the
+ *        concatenated output pixels of all levels (level after level, each in b, y, x order; P of them) are cut into
+ *        chunks = ceil(P / ppb) runs of ppb = ceil(P / clamp(P / 256, 1, 512)) pixels, a workgroup stores one partial per
+ *        (chunk, tap, channel) -- row k*k is the bias column -- into `workspace`, and the second launch adds the chunks in ascending
+ *        order.  The split depends on the shapes only, never on ssdk_set_deterministic: both modes give the same bits.
+ *   workspace: ssdk_..._group_workspace_bytes() = chunks * (k*k + 1) * channels * 4 bytes (16-byte aligned; < 0 on bad arguments);
+ *        a smaller workspace_bytes is refused.  Not needed (may be NULL) when dw and db are both NULL. */
+long long ssdk_depthwise_conv2d_group_workspace_bytes(const int* hs, const int* ws, int n_levels, int batch, int channels, int ksize,
+                                                      int stride, int pad);
+int ssdk_depthwise_conv2d_group_fwd(const float* const* xs, const int* hs, const int* ws, int n_levels, const float* w, const float* bias,
+                                    int batch, int channels, int ksize, int stride, int pad, float* const* ys, void* stream);
+int ssdk_depthwise_conv2d_group_bwd(const float* const* xs, const int* hs, const int* ws, int n_levels, const float* w,
+                                    const float* const* dys, int batch, int channels, int ksize, int stride, int pad,
+                                    float* const* dxs /* NULL, or NULL entries: no data gradient */, float* dw, float* db /* may be NULL */,
+                                    void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- depthwise feature pyramid (Tiny-DSOD D-FPN, bf/modules/features.py:123-212) ------------------------------------------------
  * NHWC fp32, channels % 4 == 0, 16-byte aligned maps.  Arguments are checked on the host before any launch (negative status).

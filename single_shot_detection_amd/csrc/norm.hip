@@ -993,65 +993,74 @@ namespace ssdk {
 
 constexpr int kDwMaxTaps = 25;   // up to 5 x 5
 
+// One output element (4 channels of one pixel): the tap order and the fmaf chain that the single-level and the grouped kernels share.
+__device__ __forceinline__ float4 dw_fwd_point(const float4* x, const float* w, const float* bias, int Hin, int Win, int C4,
+                                               int ks, int taps, int stride, int pad, int Hout, int Wout, long long i) {
+    const int c4 = (int)(i % C4);
+    long long p = i / C4;
+    const int xo = (int)(p % Wout); p /= Wout;
+    const int yo = (int)(p % Hout);
+    const int b = (int)(p / Hout);
+    float4 acc = bias ? *reinterpret_cast<const float4*>(bias + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* wc = w + (long long)c4 * 4 * taps;
+    for (int ky = 0; ky < ks; ++ky) {
+        const int iy = yo * stride - pad + ky;
+        if (iy < 0 || iy >= Hin) continue;
+        for (int kx = 0; kx < ks; ++kx) {
+            const int ix = xo * stride - pad + kx;
+            if (ix < 0 || ix >= Win) continue;
+            const float4 v = x[((long long)(b * Hin + iy) * Win + ix) * C4 + c4];
+            const int t = ky * ks + kx;
+            acc.x = fmaf(wc[t], v.x, acc.x);
+            acc.y = fmaf(wc[taps + t], v.y, acc.y);
+            acc.z = fmaf(wc[2 * taps + t], v.z, acc.z);
+            acc.w = fmaf(wc[3 * taps + t], v.w, acc.w);
+        }
+    }
+    return acc;
+}
+
 __global__ void __launch_bounds__(256) dw_fwd_kernel(const float4* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, int B, int Hin,
                                                      int Win, int C4, int ks, int stride, int pad, int Hout, int Wout, float4* __restrict__ y) {
     const long long total = (long long)B * Hout * Wout * C4;
     const int taps = ks * ks;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(i % C4);
-        long long p = i / C4;
-        const int xo = (int)(p % Wout); p /= Wout;
-        const int yo = (int)(p % Hout);
-        const int b = (int)(p / Hout);
-        float4 acc = bias ? *reinterpret_cast<const float4*>(bias + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float* wc = w + (long long)c4 * 4 * taps;
-        for (int ky = 0; ky < ks; ++ky) {
-            const int iy = yo * stride - pad + ky;
-            if (iy < 0 || iy >= Hin) continue;
-            for (int kx = 0; kx < ks; ++kx) {
-                const int ix = xo * stride - pad + kx;
-                if (ix < 0 || ix >= Win) continue;
-                const float4 v = x[((long long)(b * Hin + iy) * Win + ix) * C4 + c4];
-                const int t = ky * ks + kx;
-                acc.x = fmaf(wc[t], v.x, acc.x);
-                acc.y = fmaf(wc[taps + t], v.y, acc.y);
-                acc.z = fmaf(wc[2 * taps + t], v.z, acc.z);
-                acc.w = fmaf(wc[3 * taps + t], v.w, acc.w);
-            }
-        }
-        y[i] = acc;
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        y[i] = dw_fwd_point(x, w, bias, Hin, Win, C4, ks, taps, stride, pad, Hout, Wout, i);
 }
 
 // dx[b,iy,ix,c] = sum over taps with (iy + pad - ky) % stride == 0 ... of w[c][tap] * dy[b,(iy+pad-ky)/stride,(ix+pad-kx)/stride,c]
+// (one input element, added to `acc`: shared by the single-level and the grouped kernels)
+__device__ __forceinline__ float4 dw_dgrad_point(const float4* dy, const float* w, int Hin, int Win, int C4, int ks, int taps,
+                                                 int stride, int pad, int Hout, int Wout, long long i, float4 acc) {
+    const int c4 = (int)(i % C4);
+    long long p = i / C4;
+    const int ix = (int)(p % Win); p /= Win;
+    const int iy = (int)(p % Hin);
+    const int b = (int)(p / Hin);
+    const float* wc = w + (long long)c4 * 4 * taps;
+    for (int ky = 0; ky < ks; ++ky) {
+        const int ty = iy + pad - ky;
+        if (ty < 0 || ty % stride || ty / stride >= Hout) continue;
+        for (int kx = 0; kx < ks; ++kx) {
+            const int tx = ix + pad - kx;
+            if (tx < 0 || tx % stride || tx / stride >= Wout) continue;
+            const float4 v = dy[((long long)(b * Hout + ty / stride) * Wout + tx / stride) * C4 + c4];
+            const int t = ky * ks + kx;
+            acc.x = fmaf(wc[t], v.x, acc.x);
+            acc.y = fmaf(wc[taps + t], v.y, acc.y);
+            acc.z = fmaf(wc[2 * taps + t], v.z, acc.z);
+            acc.w = fmaf(wc[3 * taps + t], v.w, acc.w);
+        }
+    }
+    return acc;
+}
+
 __global__ void __launch_bounds__(256) dw_dgrad_kernel(const float4* __restrict__ dy, const float* __restrict__ w, int B, int Hin, int Win, int C4, int ks,
                                                        int stride, int pad, int Hout, int Wout, float4* __restrict__ dx, int accumulate) {
     const long long total = (long long)B * Hin * Win * C4;
     const int taps = ks * ks;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c4 = (int)(i % C4);
-        long long p = i / C4;
-        const int ix = (int)(p % Win); p /= Win;
-        const int iy = (int)(p % Hin);
-        const int b = (int)(p / Hin);
-        float4 acc = accumulate ? dx[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float* wc = w + (long long)c4 * 4 * taps;
-        for (int ky = 0; ky < ks; ++ky) {
-            const int ty = iy + pad - ky;
-            if (ty < 0 || ty % stride || ty / stride >= Hout) continue;
-            for (int kx = 0; kx < ks; ++kx) {
-                const int tx = ix + pad - kx;
-                if (tx < 0 || tx % stride || tx / stride >= Wout) continue;
-                const float4 v = dy[((long long)(b * Hout + ty / stride) * Wout + tx / stride) * C4 + c4];
-                const int t = ky * ks + kx;
-                acc.x = fmaf(wc[t], v.x, acc.x);
-                acc.y = fmaf(wc[taps + t], v.y, acc.y);
-                acc.z = fmaf(wc[2 * taps + t], v.z, acc.z);
-                acc.w = fmaf(wc[3 * taps + t], v.w, acc.w);
-            }
-        }
-        dx[i] = acc;
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        dx[i] = dw_dgrad_point(dy, w, Hin, Win, C4, ks, taps, stride, pad, Hout, Wout, i, accumulate ? dx[i] : make_float4(0.f, 0.f, 0.f, 0.f));
 }
 
 // grid (C4 blocks of 64 channel-quads, pixel chunks): thread (cq, ps) = channel quad cq of the block, pixel phase ps of 4
@@ -1112,6 +1121,123 @@ __global__ void zero_small_kernel(float* a, long long na, float* b, long long nb
     }
 }
 
+// ---- the same stencil over up to 8 levels that share batch, channels and weight (the RetinaNet tower, predictors.py:33-35,67-68) ----
+// The levels' maps are packed by value into the kernel argument (as CatPieces is): no pointer table on the device.  end[l] is the
+// prefix sum of the levels' work items (float4 elements for the forward / data gradient, output pixels for the weight gradient).
+constexpr int kDwMaxLevels = 8;
+struct DwLevels {
+    const float4* src[kDwMaxLevels];   // forward: x; data gradient: dy; weight gradient: x
+    float4* dst[kDwMaxLevels];         // forward: y; data gradient: dx; weight gradient: dy (read only)
+    int hin[kDwMaxLevels], win[kDwMaxLevels], hout[kDwMaxLevels], wout[kDwMaxLevels];
+    long long end[kDwMaxLevels];
+    int n;
+};
+__device__ __forceinline__ int dw_level(const DwLevels& lv, long long i) {
+    int l = 0;
+    while (l + 1 < lv.n && i >= lv.end[l]) ++l;
+    return l;
+}
+
+__global__ void __launch_bounds__(256) dw_group_fwd_kernel(DwLevels lv, const float* __restrict__ w, const float* __restrict__ bias, int C4, int ks, int stride,
+                                                           int pad) {
+    const long long total = lv.end[lv.n - 1];
+    const int taps = ks * ks;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int l = dw_level(lv, i);
+        const long long j = i - (l ? lv.end[l - 1] : 0LL);
+        lv.dst[l][j] = dw_fwd_point(lv.src[l], w, bias, lv.hin[l], lv.win[l], C4, ks, taps, stride, pad, lv.hout[l], lv.wout[l], j);
+    }
+}
+
+__global__ void __launch_bounds__(256) dw_group_dgrad_kernel(DwLevels lv, const float* __restrict__ w, int C4, int ks, int stride, int pad) {
+    const long long total = lv.end[lv.n - 1];
+    const int taps = ks * ks;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int l = dw_level(lv, i);
+        const long long j = i - (l ? lv.end[l - 1] : 0LL);
+        lv.dst[l][j] = dw_dgrad_point(lv.src[l], w, lv.hin[l], lv.win[l], C4, ks, taps, stride, pad, lv.hout[l], lv.wout[l], j, make_float4(0.f, 0.f, 0.f, 0.f));
+    }
+}
+
+// Weight / bias gradient, stage 1.  grid (C4 blocks of QUADS channel quads, chunks of the concatenated output pixels); thread (cq, ps) =
+// channel quad cq of the block, pixel phase ps of PHASES = 256 / QUADS.  A thread walks its pixels in ascending order (level after
+// level), the workgroup adds its phases in ascending order through LDS and stores ONE partial per (chunk, tap, channel) -- row `taps`
+// is the bias column -- at part[(chunk * (taps + 1) + tap) * C + c].  No atomics: the bits depend on the shapes alone.
+// The kernel size is a template argument: every index of acc is then a constant and the k * k accumulators stay in registers.
+template <int QUADS, int KS>
+__global__ void __launch_bounds__(256) dw_group_wgrad_kernel(DwLevels lv, int C4, int stride, int pad, int pixels_per_block, float* __restrict__ part) {
+    constexpr int PHASES = 256 / QUADS, taps = KS * KS;
+    __shared__ __attribute__((aligned(16))) float s_red[2][PHASES][QUADS * 4];
+    const int cq = threadIdx.x % QUADS, ps = threadIdx.x / QUADS;
+    const int c4 = blockIdx.x * QUADS + cq;
+    const long long M = lv.end[lv.n - 1];
+    const long long p0 = (long long)blockIdx.y * pixels_per_block, p1 = p0 + pixels_per_block < M ? p0 + pixels_per_block : M;
+    float4 acc[taps];
+    float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int t = 0; t < taps; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c4 < C4 && p0 + ps < p1) {
+        int l = dw_level(lv, p0 + ps);
+        long long base = l ? lv.end[l - 1] : 0LL, end = lv.end[l];
+        const float4* x = lv.src[l];
+        const float4* dy = lv.dst[l];
+        int Hin = lv.hin[l], Win = lv.win[l], Hout = lv.hout[l], Wout = lv.wout[l];
+        for (long long p = p0 + ps; p < p1; p += PHASES) {
+            while (p >= end) {   // (p < p1 <= M = end[n - 1]: l stays below n)
+                ++l;
+                base = end; end = lv.end[l];
+                x = lv.src[l]; dy = lv.dst[l];
+                Hin = lv.hin[l]; Win = lv.win[l]; Hout = lv.hout[l]; Wout = lv.wout[l];
+            }
+            const long long q = p - base;
+            const int xo = (int)(q % Wout);
+            const int yo = (int)((q / Wout) % Hout);
+            const int b = (int)(q / ((long long)Wout * Hout));
+            const float4 g = dy[q * C4 + c4];
+            bsum.x += g.x; bsum.y += g.y; bsum.z += g.z; bsum.w += g.w;
+#pragma unroll
+            for (int t = 0; t < taps; ++t) {
+                const int iy = yo * stride - pad + t / KS, ix = xo * stride - pad + t % KS;
+                if (iy >= 0 && iy < Hin && ix >= 0 && ix < Win) {
+                    const float4 v = x[((long long)(b * Hin + iy) * Win + ix) * C4 + c4];
+                    acc[t].x = fmaf(g.x, v.x, acc[t].x);
+                    acc[t].y = fmaf(g.y, v.y, acc[t].y);
+                    acc[t].z = fmaf(g.z, v.z, acc[t].z);
+                    acc[t].w = fmaf(g.w, v.w, acc[t].w);
+                }
+            }
+        }
+    }
+    // one tap per round, two LDS buffers in turn (a round's reads end before the barrier of the next round, which precedes the writes of
+    // the round after that): thread j < QUADS * 4 owns channel blockIdx.x * QUADS * 4 + j and adds the phases in ascending order
+    const int C = C4 * 4, c = blockIdx.x * QUADS * 4 + (int)threadIdx.x;
+    float* out = part + (long long)blockIdx.y * (taps + 1) * C;
+#pragma unroll
+    for (int t = 0; t <= taps; ++t) {
+        *reinterpret_cast<float4*>(&s_red[t & 1][ps][cq * 4]) = t == taps ? bsum : acc[t < taps ? t : 0];
+        __syncthreads();
+        if (threadIdx.x < QUADS * 4 && c < C) {
+            float sum = s_red[t & 1][0][threadIdx.x];
+#pragma unroll
+            for (int k = 1; k < PHASES; ++k) sum += s_red[t & 1][k][threadIdx.x];
+            out[(long long)t * C + c] = sum;
+        }
+    }
+}
+
+// stage 2: thread (tap, channel) adds the chunks in ascending order; row `taps` of the partials is db
+__global__ void __launch_bounds__(256) dw_group_wgrad_finish_kernel(const float* __restrict__ part, int chunks, int C, int taps, float* __restrict__ dw,
+                                                                    float* __restrict__ db) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (taps + 1) * C) return;
+    const int t = i / C, c = i - t * C;
+    if ((t == taps && !db) || (t < taps && !dw)) return;
+    float sum = part[i];
+    for (int k = 1; k < chunks; ++k) sum += part[(long long)k * (taps + 1) * C + i];
+    if (t == taps) db[c] = sum;
+    else dw[(long long)c * taps + t] = sum;
+}
+
 }  // namespace ssdk
 
 static int dw_check(const char* fn, int batch, int hin, int win, int channels, int ksize, int stride, int pad) {
@@ -1163,6 +1289,131 @@ extern "C" int ssdk_depthwise_conv2d_bwd(const float* x, const float* w, const f
         hipLaunchKernelGGL(ssdk::dw_wgrad_kernel, dim3((unsigned)((c4 + 63) / 64), (unsigned)chunks), dim3(256), 0, s, reinterpret_cast<const float4*>(x),
                            reinterpret_cast<const float4*>(dy), batch, hin, win, c4, ksize, stride, pad, ho, wo, ppb, dw, db);
         SSDK_CHECK_LAUNCH("dw_wgrad_kernel");
+    }
+    return SSDK_OK;
+}
+
+// ---- grouped depthwise convolution over levels ----
+struct DwGroupPlan {
+    int ho[ssdk::kDwMaxLevels], wo[ssdk::kDwMaxLevels];
+    long long pixels;   // output pixels of all levels
+    int chunks, ppb;    // stage 1 of the weight gradient: chunks of ppb consecutive pixels (a function of the shapes only)
+};
+static int dw_group_check(const char* fn, const int* hs, const int* ws, int n_levels, int batch, int channels, int ksize, int stride, int pad, DwGroupPlan& plan) {
+    SSDK_REQUIRE(n_levels >= 1 && n_levels <= ssdk::kDwMaxLevels && hs && ws, SSDK_E_INVALID, "%s: n_levels=%d (1..%d), hs / ws %s", fn, n_levels,
+                 ssdk::kDwMaxLevels, hs && ws ? "given" : "null");
+    plan.pixels = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        char who[96];
+        snprintf(who, sizeof(who), "%s: level %d", fn, l);
+        int rc = dw_check(who, batch, hs[l], ws[l], channels, ksize, stride, pad);
+        if (rc) return rc;
+        plan.ho[l] = (hs[l] + 2 * pad - ksize) / stride + 1;
+        plan.wo[l] = (ws[l] + 2 * pad - ksize) / stride + 1;
+        SSDK_REQUIRE((long long)batch * hs[l] * ws[l] < (1LL << 31) / 4, SSDK_E_INVALID, "%s: level %d: batch * H * W = %lld is beyond the kernels' int row index", fn, l,
+                     (long long)batch * hs[l] * ws[l]);
+        plan.pixels += (long long)batch * plan.ho[l] * plan.wo[l];
+    }
+    long long chunks = plan.pixels / 256;   // >= 256 pixels per chunk ...
+    if (chunks < 1) chunks = 1;
+    if (chunks > 512) chunks = 512;         // ... and at most 512 partials per (channel, tap)
+    const long long ppb = (plan.pixels + chunks - 1) / chunks;
+    SSDK_REQUIRE(ppb < (1LL << 31), SSDK_E_INVALID, "%s: %lld output pixels are beyond the chunked reduction", fn, plan.pixels);
+    plan.ppb = (int)ppb;
+    plan.chunks = (int)((plan.pixels + ppb - 1) / ppb);
+    return SSDK_OK;
+}
+static inline unsigned dw_group_blocks(long long total) { return (unsigned)((total + 255) / 256 < 65535 ? (total + 255) / 256 : 65535); }
+
+extern "C" long long ssdk_depthwise_conv2d_group_workspace_bytes(const int* hs, const int* ws, int n_levels, int batch, int channels, int ksize, int stride,
+                                                                 int pad) {
+    DwGroupPlan plan;
+    int rc = dw_group_check("ssdk_depthwise_conv2d_group_workspace_bytes", hs, ws, n_levels, batch, channels, ksize, stride, pad, plan);
+    if (rc) return rc;
+    return (long long)plan.chunks * (ksize * ksize + 1) * channels * (long long)sizeof(float);
+}
+
+extern "C" int ssdk_depthwise_conv2d_group_fwd(const float* const* xs, const int* hs, const int* ws, int n_levels, const float* w, const float* bias, int batch,
+                                               int channels, int ksize, int stride, int pad, float* const* ys, void* stream) {
+    const char* fn = "ssdk_depthwise_conv2d_group_fwd";
+    DwGroupPlan plan;
+    int rc = dw_group_check(fn, hs, ws, n_levels, batch, channels, ksize, stride, pad, plan);
+    if (rc) return rc;
+    SSDK_REQUIRE(xs && ys && w && (((uintptr_t)w | (uintptr_t)bias) & 15) == 0, SSDK_E_INVALID, "%s: null xs / ys / w, or unaligned w / bias", fn);
+    ssdk::DwLevels lv = {};
+    const int c4 = channels / 4;
+    long long total = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        SSDK_REQUIRE(xs[l] && ys[l] && (((uintptr_t)xs[l] | (uintptr_t)ys[l]) & 15) == 0, SSDK_E_INVALID, "%s: level %d: null or unaligned x / y", fn, l);
+        lv.src[l] = reinterpret_cast<const float4*>(xs[l]);
+        lv.dst[l] = reinterpret_cast<float4*>(ys[l]);
+        lv.hin[l] = hs[l]; lv.win[l] = ws[l]; lv.hout[l] = plan.ho[l]; lv.wout[l] = plan.wo[l];
+        total += (long long)batch * plan.ho[l] * plan.wo[l] * c4;
+        lv.end[l] = total;
+    }
+    lv.n = n_levels;
+    hipLaunchKernelGGL(ssdk::dw_group_fwd_kernel, dim3(dw_group_blocks(total)), dim3(256), 0, (hipStream_t)stream, lv, w, bias, c4, ksize, stride, pad);
+    SSDK_CHECK_LAUNCH("dw_group_fwd_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_depthwise_conv2d_group_bwd(const float* const* xs, const int* hs, const int* ws, int n_levels, const float* w, const float* const* dys, int batch,
+                                               int channels, int ksize, int stride, int pad, float* const* dxs, float* dw, float* db, void* workspace,
+                                               long long workspace_bytes, void* stream) {
+    const char* fn = "ssdk_depthwise_conv2d_group_bwd";
+    DwGroupPlan plan;
+    int rc = dw_group_check(fn, hs, ws, n_levels, batch, channels, ksize, stride, pad, plan);
+    if (rc) return rc;
+    SSDK_REQUIRE(xs && dys && w && (((uintptr_t)w | (uintptr_t)dw | (uintptr_t)db) & 3) == 0, SSDK_E_INVALID, "%s: null xs / dys / w, or unaligned w / dw / db", fn);
+    const int c4 = channels / 4, taps = ksize * ksize;
+    const long long need = (long long)plan.chunks * (taps + 1) * channels * (long long)sizeof(float);
+    const bool wgrad = dw || db;
+    SSDK_REQUIRE(!wgrad || (workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0), SSDK_E_INVALID,
+                 "%s: workspace of %lld bytes (%s), ssdk_depthwise_conv2d_group_workspace_bytes says %lld", fn, workspace_bytes,
+                 workspace ? "given" : "null", need);
+    ssdk::DwLevels dg = {}, wg = {};
+    long long dg_total = 0, wg_total = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        SSDK_REQUIRE(xs[l] && dys[l] && (((uintptr_t)xs[l] | (uintptr_t)dys[l] | (uintptr_t)(dxs ? dxs[l] : nullptr)) & 15) == 0, SSDK_E_INVALID,
+                     "%s: level %d: null or unaligned x / dy / dx", fn, l);
+        wg.src[l] = reinterpret_cast<const float4*>(xs[l]);
+        wg.dst[l] = const_cast<float4*>(reinterpret_cast<const float4*>(dys[l]));   // (read only in the weight gradient)
+        wg.hin[l] = hs[l]; wg.win[l] = ws[l]; wg.hout[l] = plan.ho[l]; wg.wout[l] = plan.wo[l];
+        wg_total += (long long)batch * plan.ho[l] * plan.wo[l];
+        wg.end[l] = wg_total;
+        if (dxs && dxs[l]) {   // the data gradient runs over the levels that ask for one
+            const int k = dg.n++;
+            dg.src[k] = reinterpret_cast<const float4*>(dys[l]);
+            dg.dst[k] = reinterpret_cast<float4*>(dxs[l]);
+            dg.hin[k] = hs[l]; dg.win[k] = ws[l]; dg.hout[k] = plan.ho[l]; dg.wout[k] = plan.wo[l];
+            dg_total += (long long)batch * hs[l] * ws[l] * c4;
+            dg.end[k] = dg_total;
+        }
+    }
+    wg.n = n_levels;
+    hipStream_t s = (hipStream_t)stream;
+    if (dg.n) {
+        hipLaunchKernelGGL(ssdk::dw_group_dgrad_kernel, dim3(dw_group_blocks(dg_total)), dim3(256), 0, s, dg, w, c4, ksize, stride, pad);
+        SSDK_CHECK_LAUNCH("dw_group_dgrad_kernel");
+    }
+    if (wgrad) {
+        float* part = reinterpret_cast<float*>(workspace);
+        // the workgroup's split of its 256 threads: full at C4 = 16 (64 channels) and 32 (128 channels), dw_wgrad_kernel's from there on
+        const int quads = c4 <= 16 ? 16 : c4 <= 32 ? 32 : 64;
+        const dim3 grid((unsigned)((c4 + quads - 1) / quads), (unsigned)plan.chunks);
+        void (*kernel)(ssdk::DwLevels, int, int, int, int, float*) = nullptr;
+#define SSDK_DW_GROUP_WGRAD(K) \
+    case K: kernel = quads == 16 ? ssdk::dw_group_wgrad_kernel<16, K> : quads == 32 ? ssdk::dw_group_wgrad_kernel<32, K> : ssdk::dw_group_wgrad_kernel<64, K>; break;
+        switch (ksize) {
+            SSDK_DW_GROUP_WGRAD(1) SSDK_DW_GROUP_WGRAD(2) SSDK_DW_GROUP_WGRAD(3) SSDK_DW_GROUP_WGRAD(4) SSDK_DW_GROUP_WGRAD(5)
+        }
+#undef SSDK_DW_GROUP_WGRAD
+        SSDK_REQUIRE(kernel, SSDK_E_INVALID, "%s: k=%d", fn, ksize);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, wg, c4, stride, pad, plan.ppb, part);
+        SSDK_CHECK_LAUNCH("dw_group_wgrad_kernel");
+        const int n = (taps + 1) * channels;
+        hipLaunchKernelGGL(ssdk::dw_group_wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, plan.chunks, channels, taps, dw, db);
+        SSDK_CHECK_LAUNCH("dw_group_wgrad_finish_kernel");
     }
     return SSDK_OK;
 }

@@ -2,7 +2,7 @@
 SHARED across levels, then ReLU, then a BatchNorm PER LEVEL; separate score and loc towers).  Module nesting and names
 follow the reference so checkpoints map 1:1.  Each tower layer is ONE grouped implicit-GEMM launch over the five
 levels (shared weights, ReLU fused into the epilogue, csrc/conv.hip) followed by the per-level BatchNorm kernels
-(csrc/norm.hip)."""
+(csrc/norm.hip); with ``use_depthwise`` the shared depthwise stencil of the five levels is one launch in front of it."""
 import functools
 
 import torch.nn as nn
@@ -42,17 +42,25 @@ class SharedConvPredictor(nn.Module):
         self.convs.apply(_init_predictor)
 
     def _layer(self, block, norms, xs):
-        if isinstance(block, conv.Conv2dBn) and isinstance(self.activation, nn.ReLU) and block._hip_ok():
-            c = block.conv
+        depthwise = isinstance(block, conv.DepthwiseConv2dBn) and len(block._modules) == 2 and 1 <= len(xs) <= 8   # (the tower's: two bare convolutions)
+        if (depthwise or isinstance(block, conv.Conv2dBn)) and isinstance(self.activation, nn.ReLU) and block._hip_ok():
+            xs = list(xs)
+            if depthwise:
+                # the shared depthwise stencil of all levels in ONE launch (ops.depthwise_conv2d on a list), then the shared pointwise 1 x 1
+                d, c = block.depthwise_conv, block.pointwise_conv
+                xs = ops.depthwise_conv2d(xs, d.weight, d.bias, stride=d.stride[0], padding=d.padding[0])
+            else:
+                c = block.conv
             if all(type(norm) is nn.BatchNorm2d and norm.training and ops.sync_group_of(norm) is None for norm in norms):
                 # per-process statistics: taken in the shared convolution's epilogue, level by level (ops.conv2d_batch_norm)
-                return ops.conv2d_batch_norm(list(xs), c.weight, c.bias, c.stride[0], c.padding[0], list(norms), conv_relu=True, bn_relu=False)
-            ys = ops.conv2d(list(xs), c.weight, c.bias, stride=c.stride[0], padding=c.padding[0], relu=True)
+                return ops.conv2d_batch_norm(xs, c.weight, c.bias, c.stride[0], c.padding[0], list(norms), conv_relu=True, bn_relu=False)
+            ys = ops.conv2d(xs, c.weight, c.bias, stride=c.stride[0], padding=c.padding[0], relu=True)
             if all(type(norm) is nn.BatchNorm2d for norm in norms):
                 # per-level norms; marked for synchronisation (detection.init(distributed=True)) the five share ONE all-reduce
                 return ops.batch_norm_levels(ys, list(norms))
             return [ops.batch_norm(y, norm) if type(norm) is nn.BatchNorm2d else norm(y) for norm, y in zip(norms, ys)]
-        return [norm(self.activation(block(x))) for norm, x in zip(norms, xs)]   # depthwise towers: stock ops
+        # any other activation or block shape: level by level, the block's own forward and the stock activation / norm modules
+        return [norm(self.activation(block(x))) for norm, x in zip(norms, xs)]
 
     def forward(self, sources):  # predictors.py:60-76: conv -> activation -> per-level norm
         score_sources = loc_sources = list(sources)

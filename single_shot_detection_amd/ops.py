@@ -1103,8 +1103,77 @@ class _DepthwiseFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+class _DepthwiseGroupFn(torch.autograd.Function):
+    """The depthwise convolution of n <= 8 maps that share weight and bias (the levels of a RetinaNet tower layer,
+    detection/modules/predictors.py:33-35,67-68): one launch forward, one for the data gradients, two for dw / db
+    (ssdk_depthwise_conv2d_group_*; no atomics, the same bits in both modes of ``set_deterministic``).
+    apply(weight, bias, stride, pad, x_0, x_1, ...) -> y_0, y_1, ..."""
+
+    @staticmethod
+    def _levels(xs):
+        import ctypes
+        n = len(xs)
+        hs = (ctypes.c_int * n)(*[x.shape[2] for x in xs])
+        ws = (ctypes.c_int * n)(*[x.shape[3] for x in xs])
+        return n, hs, ws
+
+    @staticmethod
+    def _ptrs(ts):
+        import ctypes
+        return (ctypes.c_void_p * len(ts))(*[_dp(t) for t in ts])
+
+    @staticmethod
+    def forward(ctx, weight, bias, stride, pad, *xs):
+        lib = _lib.lib()
+        _lib.require_cuda(weight, *xs)
+        xs = [_nhwc(x) for x in xs]
+        B, C = xs[0].shape[:2]
+        if any(x.shape[0] != B or x.shape[1] != C for x in xs):
+            raise ValueError('depthwise_conv2d: the maps of a list share batch and channels; got ' + str([tuple(x.shape) for x in xs]))
+        k = weight.shape[-1]
+        w = weight.float().contiguous()
+        b = None if bias is None else bias.float().contiguous()
+        ys = [torch.empty((B, C, _out_dim(x.shape[2], k, stride, pad), _out_dim(x.shape[3], k, stride, pad)), dtype=torch.float32, device=x.device,
+                          memory_format=torch.channels_last) for x in xs]
+        n, hs, ws = _DepthwiseGroupFn._levels(xs)
+        _lib.check(lib.ssdk_depthwise_conv2d_group_fwd(_DepthwiseGroupFn._ptrs(xs), hs, ws, n, _dp(w), _dp(b), B, C, k, stride, pad,
+                                                       _DepthwiseGroupFn._ptrs(ys), _lib.current_stream()), 'ssdk_depthwise_conv2d_group_fwd')
+        ctx.save_for_backward(w, *xs)
+        ctx.meta = (stride, pad, bias is not None)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        lib = _lib.lib()
+        w, xs = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        stride, pad, has_bias = ctx.meta
+        B, C = xs[0].shape[:2]
+        k = w.shape[-1]
+        n, hs, ws = _DepthwiseGroupFn._levels(xs)
+        dys = [torch.zeros((B, C, _out_dim(x.shape[2], k, stride, pad), _out_dim(x.shape[3], k, stride, pad)), dtype=torch.float32, device=x.device,
+                           memory_format=torch.channels_last) if dy is None else _nhwc(dy) for x, dy in zip(xs, dys)]
+        dxs = [torch.empty_like(x, memory_format=torch.channels_last) if need else None for x, need in zip(xs, ctx.needs_input_grad[4:])]
+        want_w = ctx.needs_input_grad[0] or (has_bias and ctx.needs_input_grad[1])
+        dw = torch.empty_like(w) if want_w else None
+        db = torch.empty((C,), dtype=torch.float32, device=w.device) if want_w and has_bias else None
+        work, nbytes = None, 0
+        if want_w:
+            nbytes = lib.ssdk_depthwise_conv2d_group_workspace_bytes(hs, ws, n, B, C, k, stride, pad)
+            if nbytes < 0:
+                _lib.check(int(nbytes), 'ssdk_depthwise_conv2d_group_workspace_bytes')
+            work = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        if want_w or any(d is not None for d in dxs):
+            _lib.check(lib.ssdk_depthwise_conv2d_group_bwd(_DepthwiseGroupFn._ptrs(xs), hs, ws, n, _dp(w), _DepthwiseGroupFn._ptrs(dys), B, C, k, stride, pad,
+                                                           _DepthwiseGroupFn._ptrs(dxs), _dp(dw), _dp(db), _dp(work), nbytes, _lib.current_stream()),
+                       'ssdk_depthwise_conv2d_group_bwd')
+        return (dw if ctx.needs_input_grad[0] else None, db if has_bias and ctx.needs_input_grad[1] else None, None, None) + tuple(dxs)
+
+
 def depthwise_conv2d(x, weight, bias=None, stride=1, padding=0):
-    return _DepthwiseFn.apply(x, weight, bias, int(stride), int(padding))
+    """Depthwise convolution of a map, or of a list of at most 8 maps that share the weights (one launch; returns a list)."""
+    if isinstance(x, torch.Tensor):
+        return _DepthwiseFn.apply(x, weight, bias, int(stride), int(padding))
+    return list(_DepthwiseGroupFn.apply(weight, bias, int(stride), int(padding), *x))
 
 
 # ---- depthwise feature pyramid (Tiny-DSOD D-FPN, bf/modules/features.py:123-212) ------------------------------------------------
