@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 119
+#define SSDK_VERSION 120
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -506,6 +506,20 @@ int ssdk_conv2d_bwd_fast(const ssdk_conv_desc* descs, int n, int batch, int accu
  * layers of a chain, the results passed as ssdk_conv_desc::w_t (the reference has no counterpart: cuDNN re-lays weights out inside
  * every backward call, bf/modules/conv.py:30-36 through torch.nn.Conv2d). */
 int ssdk_conv2d_transpose_weights(const ssdk_conv_desc* descs, int n, float* const* outs, void* stream);
+/* TEST HOOK, host only (no device, no pointer is dereferenced: the descriptors' pointers are looked at for NULL and 16-byte alignment):
+ * the GEMM launches that ssdk_conv2d_fwd_ws (direction 0) or the data-gradient part of ssdk_conv2d_bwd / _bwd_sk (direction 1; descriptors
+ * without dx make none) would make for these descriptors, decided by the code, the environment and the deterministic flag the real call
+ * uses.  have_workspace: a stream-K workspace would be passed.  One entry per launch (direction 1: stride-1, strided scatter, strided
+ * ordered -- at most 3): kernel = the instantiation ("dma generic one-tile", "staged<4> mirror", "streamk", "... + strided_dx" when the
+ * sum pass follows); per problem, in the order of the launch's descriptors (desc[i] = index in descs): column blocks, K splits, half-width
+ * last tile, first workgroup and workgroup count in the grouped grid. */
+typedef struct ssdk_conv_plan_launch {
+    char kernel[48];
+    int grid, count;
+    int desc[8], n_blocks[8], k_splits[8], half_last[8], block_begin[8], blocks[8];
+} ssdk_conv_plan_launch;
+int ssdk_debug_conv2d_plan(const ssdk_conv_desc* descs, int n, int batch, int direction, int have_workspace, ssdk_conv_plan_launch* out,
+                           int max_launches, int* n_launches);
 /* dx = y > 0 ? dy : 0 (n floats, n % 4 == 0). */
 int ssdk_relu_bwd(const float* y, const float* dy, long long n, float* dx, void* stream);
 

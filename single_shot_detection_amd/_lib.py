@@ -87,6 +87,7 @@ _SIGNATURES = {
     'ssdk_nms': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'ssdk_debug_heads_bwd_layout': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+    'ssdk_debug_conv2d_plan': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     'ssdk_heads_bwd_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     'ssdk_heads_bwd': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -197,6 +198,12 @@ class ConvDesc(C.Structure):
                 ('bias', C.c_void_p), ('cout', C.c_int), ('ksize', C.c_int), ('stride', C.c_int), ('pad', C.c_int),
                 ('relu', C.c_int), ('y', C.c_void_p), ('dy', C.c_void_p), ('dx', C.c_void_p), ('dw', C.c_void_p),
                 ('db', C.c_void_p), ('w_t', C.c_void_p), ('stats', C.c_void_p)]
+
+
+class ConvPlanLaunch(C.Structure):
+    """ssdk_conv_plan_launch (include/ssdk.h)."""
+    _fields_ = [('kernel', C.c_char * 48), ('grid', C.c_int), ('count', C.c_int), ('desc', C.c_int * 8), ('n_blocks', C.c_int * 8),
+                ('k_splits', C.c_int * 8), ('half_last', C.c_int * 8), ('block_begin', C.c_int * 8), ('blocks', C.c_int * 8)]
 
 
 def exported_symbols():

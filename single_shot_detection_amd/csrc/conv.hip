@@ -43,65 +43,18 @@
 #include <mutex>
 
 #include "common.h"
+#include "conv_plan.h"
 
 namespace ssdk {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBM = 128;        // output pixels per workgroup
-constexpr int kBK = 32;         // K slice
 constexpr int kLdsStride = 36;  // floats per LDS row (32 + 4 pad)
-constexpr int kMaxTN = 4;       // 32-wide column tiles per workgroup
-constexpr int kConvThreads = 256;
-constexpr int kMaxProblems = 8;
 #ifndef SSDK_CONV_WAVES
 #define SSDK_CONV_WAVES 2  // workgroups per CU the GEMM kernels are register-budgeted for: 2 -> <=256 VGPRs, no spills
                            // (measured: the 3-workgroup budget of 168 VGPRs spills the prefetch registers and is 10% slower)
 #endif
-
-struct ConvProblem {
-    // A operand rows [pixel][channel], one segment
-    const float* a;
-    long long a_bstride;  // per-image stride (floats)
-    int a_pstride;        // per-pixel stride (floats)
-    int Cc;               // channels (K per tap)
-    int B, Hout, Wout, Hin, Win, ksize, stride, pad;
-    // W rows: n < n0 -> w0[n][taps*Cc], else w1[n-n0][taps*Cc]
-    const float* w0;
-    const float* w1;
-    const float* bias0;
-    const float* bias1;
-    int n0, n1;
-    // output: element (image b, pixel p, channel n) at o0 + b*ob0 + p*os0 + n (n < n0) / o1 + b*ob1 + p*os1 + (n-n0)
-    float* o0;
-    float* o1;
-    long long ob0, ob1;
-    int os0, os1;
-    int tiles_n, n_blocks, m_tiles;
-    int m_tiles256;   // M tiles of the 8-wave (256-pixel) tiling
-    int k_splits;     // > 1: the K slices are divided over k_splits workgroups that atomically add into a zeroed output
-    int block_begin;  // first workgroup of this problem in the grouped grid
-    int relu;
-    // device-side mode switch (sparse backward): the launch is a no-op for this problem unless *mode == want_mode
-    const int* mode;
-    int want_mode;
-    // SCATTER instantiation: rows are the entries of row_list (pixel ids with a non-zero gradient row), *row_count of them
-    const int* row_list;
-    const int* row_count;
-    int sc_cin;  // scatter: output channels per tap (n = tap * sc_cin + c)
-    // column index space: [0, n0) = rows of w0, [n0, n0_pad) unused, [n0_pad, n0_pad + n1) = rows of w1.  n0_pad = n0 except for
-    // the LDS-DMA kernel, which rounds it up to 8 so that every 8-row DMA piece reads ONE weight tensor (one descriptor)
-    int n0_pad;
-    unsigned w0_bytes, w1_bytes;   // LDS-DMA kernel: sizes of the two weight tensors (buffer descriptors)
-    int forced;   // n_blocks / k_splits were set by the caller: launch_group keeps them
-    // The last 32-column tile holds at most 16 columns (N = 104 of the 21-class heads: 3 tiles + 8 columns): it is computed as a 16-column
-    // tile by v_mfma_f32_16x16x1_4b_f32 at half the cycles of a 32 x 32 x 2 (dma_tile, forward LDS-DMA form only; set by launch_group)
-    int half_last;
-    // BatchNorm statistics of the output, fused into the epilogue (forward, one output, not split over K): per-column sums of the
-    // stored values and of their squares are ADDED into stats[0 .. n0) / stats[n0 .. 2 n0) (fp64), stats[2 n0] = rows.  NULL: none.
-    double* stats;
-};
 
 struct ConvGroup {
     int count;
@@ -2879,132 +2832,84 @@ struct ZeroList {
     }
 };
 
-static void finish_problem(ConvProblem& g) {
-    g.n0_pad = g.n0;
-    const int N = g.n0 + g.n1;
-    g.tiles_n = cdiv(N, 32);
-    g.n_blocks = cdiv(g.tiles_n, kMaxTN);
-    g.m_tiles = cdiv(g.B * g.Hout * g.Wout, kBM);
-    g.m_tiles256 = cdiv(g.B * g.Hout * g.Wout, 256);
-    g.k_splits = 1;
-}
-static long long problem_block_work(const ConvProblem& g) {
-    const int chunks = cdiv(g.Cc, kBK);
-    return (long long)g.ksize * g.ksize * chunks * cdiv(g.tiles_n, g.n_blocks) / g.k_splits;
-}
-// small GEMMs (pyramid tail): too few output tiles to fill 256 CUs -> split K, add partial tiles atomically (the
-// caller zeroes the output first).  Not with a fused ReLU (needs the complete sum).
-static bool maybe_split_k_any(ConvProblem& g);
-static bool maybe_split_k(ConvProblem& g) {
-    if (!deterministic()) return maybe_split_k_any(g);
-    // deterministic mode: a K split adds its partial tiles with fp32 atomics in hardware order -- never taken (the column-block choices
-    // that come without a split are kept)
-    ConvProblem t = g;
-    maybe_split_k_any(t);
-    if (t.k_splits == 1) g = t;
-    return false;
-}
-static bool maybe_split_k_any(ConvProblem& g) {
-    const int blocks = cdiv(g.m_tiles, 8) * 8 * g.n_blocks;
-    const int slices = g.ksize * g.ksize * cdiv(g.Cc, kBK);
-    static const bool old_rules = getenv("SSDK_CONV_OLD_SPLIT") != nullptr;   // (measurement knob: the rules before round 4's sweep)
-    // A K chain of eight slices is not worth cutting: a split saves at most ~3 us of it and costs a zero-fill launch, an atomic epilogue
-    // and -- for a convolution in front of a BatchNorm -- the statistics pass that a complete tile does in its epilogue
-    // (tools/conv_decomp_sweep.py m2det: 1 x 1 256 -> 256 at 16 x 16, batch 16: 19.4 -> 13.6 us with 32-column workgroups and no split)
-    static const int no_split_upto = []() { const char* e = getenv("SSDK_CONV_NO_SPLIT_UPTO"); return e ? atoi(e) : 8; }();   // (measurement knob: 16 and 24 measured within noise of 8 on SSD-300 / SSD-512 / M2Det)
-    if (g.relu || blocks >= 256 || slices < (old_rules ? 8 : no_split_upto + 1)) return false;
-    // Many row tiles, few column blocks (the SSD-300 tail's 1 x 1 512 -> 256 at 18 x 18, batch 32: 81 x 2 tiles of 128 x 128): 64-column
-    // workgroups fill the chip WITHOUT splitting K -- no atomic epilogue (3 x the output through 1.3 TB/s of atomics), no zero-fill
-    // launch: 57 -> 44 us (tools/conv_decomp_sweep.py; the other tail layers stay within 15 % of their best split)
-    if (g.tiles_n >= 4 && g.tiles_n % 2 == 0 && (long long)g.m_tiles * (g.tiles_n / 2) >= 256 && slices <= 32) {
-        g.n_blocks = g.tiles_n / 2;
-        g.forced = 1;
-        return false;
+// ---- the environment: conv_knob() is the one getenv of this file (the table -- name, read time, default, meaning -- is kConvKnobs) -------
+static const char* conv_knob(ConvKnob k) { return getenv(kConvKnobs[k].name); }
+static bool knob_set(ConvKnob k) { return conv_knob(k) != nullptr; }
+static bool knob_nonzero(ConvKnob k) { const char* e = conv_knob(k); return e && atoi(e) != 0; }
+static int knob_int(ConvKnob k, int dflt) { const char* e = conv_knob(k); return e ? atoi(e) : dflt; }
+static int knob_positive(ConvKnob k, int dflt) { const char* e = conv_knob(k); const int v = e ? atoi(e) : 0; return v > 0 ? v : dflt; }
+static long long knob_positive_ll(ConvKnob k, long long dflt) { const char* e = conv_knob(k); const long long v = e ? atoll(e) : 0; return v > 0 ? v : dflt; }
+
+// The knob values of one launch plan.  The 'P' knobs are read at the first plan of the process; a 'C' knob is read only where the request
+// and the problems leave it a say (the LDS-DMA experiments not for operands the LDS-DMA kernel cannot take, the stream-K ones not without a
+// workspace, ...): what is not read stays false and is not looked at by plan_launch.
+static PlanKnobs read_plan_knobs(const ConvProblem* probs, int count, ConvForm form, bool vtab, bool ws, ConvSplit split) {
+    static const PlanKnobs once = []() {
+        PlanKnobs k{};
+        k.old_split = knob_set(K_CONV_OLD_SPLIT);
+        k.no_split_upto = knob_int(K_CONV_NO_SPLIT_UPTO, 8);
+        k.split_wide = knob_int(K_CONV_SPLIT_WIDE, 256);
+        const char* e = conv_knob(K_CONV_STREAMK_GENERIC);
+        k.streamk_generic = !e ? -1 : (atoi(e) ? 1 : 0);
+        k.streamk_bwd = knob_nonzero(K_CONV_STREAMK_BWD);
+        k.narrow_to = knob_positive_ll(K_CONV_NARROW_TO, 256);
+        return k;
+    }();
+    PlanKnobs k = once;
+    const bool plain = form == kFormPlain, mirror = form == kFormMirror, scatter = form == kFormScatter;
+    const RowForm rf = row_form(probs, count);
+    bool chunks = true, half = false;   // whole 32-channel chunks everywhere; some column space ends in a tile of <= 16 columns
+    for (int i = 0; i < count; ++i) {
+        const ConvProblem& g = probs[i];
+        chunks = chunks && g.Cc % kBK == 0;
+        half = half || half_tile_of((g.n1 > 0 ? cdiv(g.n0, 8) * 8 : g.n0) + g.n1);   // (whatever g.stats: a split drops them)
     }
-    // Few row tiles and a deep K (the 3 x 3 / 2 layers on 16 x 16 .. 4 x 4 maps: M <= 1 024 rows, 36 .. 72 slices): 32-column workgroups
-    // first, then only as many K splits as bring the launch to ~256 workgroups with at least 8 slices each -- the rule below split the
-    // M2Det TUM's 256 -> 256 layer at 16 x 16 eighteen ways (49 us; 26 us with 8 column blocks x 4 splits), tools/conv_decomp_sweep.py
-    // (round 4: up to 32 row tiles when tiles x column tiles still fit one per CU -- the M2Det TUM's 256 -> 256 layer at 32 x 32 -> 16 x 16,
-    // batch 16, took the rule below: 2 column blocks x 8 splits, 73.5 us; 8 column blocks x 2 splits: 52.6)
-    static const int wide = []() { const char* e = getenv("SSDK_CONV_SPLIT_WIDE"); return e ? atoi(e) : 256; }();   // (measurement knob)
-    if (g.m_tiles >= 3 && (g.m_tiles <= 8 || (!old_rules && g.m_tiles <= 32 && g.m_tiles * g.tiles_n <= wide)) && slices >= 32) {   // (one or two row tiles: the rule below measured as good or better)
-        g.n_blocks = g.tiles_n;
-        int ks = std::max(2, 256 / std::max(1, g.m_tiles * g.n_blocks));
-        ks = std::min(ks, slices / 8);
-        if (!old_rules && g.m_tiles > 8 && g.m_tiles * g.n_blocks * ks > 512) ks = 512 / (g.m_tiles * g.n_blocks);   // (never more than two workgroups per CU)
-        if (!old_rules && g.m_tiles > 8 && ks < 2) { g.forced = 1; return false; }   // one 32-column workgroup per tile, whole K: no atomics, statistics in the epilogue
-        if (ks >= 2) {
-            g.k_splits = ks;
-            g.forced = 1;
-            return true;
-        }
-        g.n_blocks = cdiv(g.tiles_n, kMaxTN);
+    if (rf.vec4 && !(mirror && rf.strided)) k.no_dma = knob_set(K_CONV_NO_DMA);
+    const bool dma = rf.vec4 && !(mirror && rf.strided) && !k.no_dma && chunks;
+    k.sk_minrange = 6 * kMaxTN;
+    if (ws && chunks) {
+        k.no_streamk = knob_set(K_CONV_NO_STREAMK);
+        if (!plain && !k.no_streamk && k.streamk_generic != 0 && (!mirror || k.streamk_bwd)) k.sk_minrange = knob_positive_ll(K_SK_MINRANGE, 6 * kMaxTN);
     }
-    int ks = cdiv(512, blocks);
-    if (ks > slices / 4) ks = slices / 4;
-    if (ks < 2) return false;
-    g.k_splits = ks;
-    return true;
-}
-// Atomic epilogues (split K, scatter) leave a CU at about one 256-byte wave instruction per 50 ns (MI355X_MICROARCH.md, Global
-// float atomics): the 256 of a 128-column tile take 13 us -- phase stamps of the pyramid tail's convolutions showed 3 us of
-// prologue, 8 us of K loop and 13 us of epilogue.  While the launch is smaller than the chip, halve the columns per workgroup
-// instead: twice the workgroups, each with half the atomics, on CUs that were idle.
-static void narrow_for_atomics(ConvProblem& g) {
-    while (g.n_blocks < g.tiles_n && (long long)g.m_tiles * g.n_blocks * g.k_splits <= 256) g.n_blocks = std::min(g.tiles_n, g.n_blocks * 2);
+    if (split == kSplitHeads) {   // (asked only of a launch small enough to split, as plan_launch counts it)
+        long long blocks = 0;
+        for (int i = 0; i < count; ++i) blocks += (long long)cdiv(cdiv(probs[i].B * probs[i].Hout * probs[i].Wout, kBM), 8) * 8 * cdiv(cdiv(probs[i].n0 + probs[i].n1, 32), kMaxTN);
+        if (blocks <= kStreamKWgs) k.heads_no_splitk = knob_set(K_HEADS_NO_SPLITK);
+    }
+    if (!vtab && !(plain && ws)) k.no_narrow = knob_set(K_CONV_NO_NARROW);
+    if (dma) {
+        if (plain) k.bk16 = knob_set(K_CONV_BK16);
+        if (plain && !k.bk16) k.tn6 = knob_set(K_CONV_TN6);
+        if (!scatter) k.w8 = knob_set(K_CONV_W8);
+        if (!vtab && !(plain && ws)) k.no_3stage = knob_set(K_CONV_NO_3STAGE);
+    }
+    if (half && !mirror && !scatter && (dma || (ws && chunks))) k.no_half_tile = knob_set(K_CONV_NO_HALF_TILE);
+    return k;
 }
 
-// decides the kernel (LDS-DMA or register staged; 128- or 256-pixel tiles), orders the problems by decreasing work per
-// workgroup (longest first), assigns block ranges, launches
-constexpr int kStreamKWgs = 512;   // two 64 KB-LDS workgroups per CU x 256 CUs: the most a stream-K launch uses, and the size its workspace is laid out for
 struct StreamKWs {
     float* partial;
     unsigned* flags;   // [kStreamKWgs + 2]: a flag per workgroup (back to 0 once consumed), then the timeout counter at [kStreamKWgs] and the launch
                        // counter of the last stream-K launch at [kStreamKWgs + 1] (FIXED places: a launch capped
                        // below kStreamKWgs workgroups -- ssdk_heads_fwd_ex -- shares the workspace with uncapped ones)
-    int nwg;
 };
-// does a column space of N end in a tile of at most 16 columns?
-static inline bool half_tile_of(int N) { return N % 32 != 0 && N % 32 <= 16; }
-constexpr long long kStreamKMinRange = 24 * kMaxTN;
-constexpr int kStreamKMinWgs = 256;
-// generic convolutions (pyramid tail, tower, necks): the launches stream-K helps are ONE to two rounds of tiles on 256 CUs (the SSD-300
-// tail's 1 x 1 512 -> 256 at 18 x 18: 162 tiles of 128 x 128, split over K three ways with an atomic epilogue before), so their ranges are
-// shorter than the heads': 6 K slices of a 128-column block (SSDK_SK_MINRANGE: measurement knob)
-static long long streamk_generic_min_range() {
-    const char* e = getenv("SSDK_SK_MINRANGE");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? v : 6 * kMaxTN;
+static StreamKWs carve_streamk(void* workspace) {
+    Carver c(workspace);
+    StreamKWs sk;
+    sk.partial = c.take<float>((size_t)(kStreamKWgs + 1) * (4 * kMaxTN * 4 * 64 * 4));
+    sk.flags = c.take<unsigned>((size_t)kStreamKWgs + 2);
+    return sk;
 }
-// would launch_group run these forward problems in stream-K form? (decided before the caller splits K: a split launch never does)
-static bool streamk_would_take(const ConvProblem* probs, int count, bool generic, bool mirror = false) {
-    // generic convolutions: OFF unless asked for (SSDK_CONV_STREAMK_GENERIC=1).  Measured on the SSD-300 tail at batch 32
-    // (tools/r03_sk_sweep.sh): the 1 x 1 512 -> 256 layer 56 -> 92-115 us and the 3 x 3 / 2 256 -> 512 layer 85 -> 140 us with ranges of
-    // 8 .. 32 units -- a launch of ONE round has no tail to even out, and every workgroup then parks and fixes up a 64 KB partial tile
-    // Round 4: launches of TWO rounds of tiles and more do take it (the RetinaNet tower's grouped launches: 2 664 tiles of 128 x 128 on 512
-    // slots -- the last, partly filled round is what stream-K evens out: 46.40 -> 45.94 ms per step); SSDK_CONV_STREAMK_GENERIC=1: every
-    // generic launch that qualifies like a heads launch, =0: none
-    static const int generic_mode = []() { const char* e = getenv("SSDK_CONV_STREAMK_GENERIC"); return !e ? -1 : (atoi(e) ? 1 : 0); }();
-    // Round 5: the mirrored-tap data gradient can take it too (igemm_streamk_kernel<true>), but does not by default: on the RetinaNet towers'
-    // grouped launch (2 688 tiles on 512 slots, 8 launches per step) it measured 1 475 us per launch against 1 478 us for the whole-tile
-    // launch and 46.13 / 46.11 against 46.12 / 46.22 ms per step -- nothing to show for the spin-waits.  SSDK_CONV_STREAMK_BWD=1 turns it on.
-    static const bool bwd_on = []() { const char* e = getenv("SSDK_CONV_STREAMK_BWD"); return e && atoi(e) != 0; }();
-    if (getenv("SSDK_CONV_NO_STREAMK") || (generic && generic_mode == 0) || (mirror && !bwd_on)) return false;
-    long long units = 0, blocks = 0;
-    for (int i = 0; i < count; ++i) {
-        const ConvProblem& g = probs[i];
-        if (g.Cc % kBK || g.mode) return false;
-        const int N = (g.n1 > 0 ? cdiv(g.n0, 8) * 8 : g.n0) + g.n1, tiles_n = cdiv(N, 32);
-        const int half = (!mirror && !g.stats && half_tile_of(N) && !getenv("SSDK_CONV_NO_HALF_TILE")) ? 1 : 0;   // (as launch_group will set half_last)
-        units += (long long)g.m_tiles * g.ksize * g.ksize * (g.Cc / kBK) * (2 * tiles_n - half);           // half-tile units, as StreamK counts
-        blocks += (long long)cdiv(g.m_tiles, 8) * 8 * cdiv(tiles_n, kMaxTN);
-    }
-    const long long min_range = generic ? streamk_generic_min_range() : kStreamKMinRange;
-    const long long nwg = std::min<long long>(512, units / (2 * min_range) / 8 * 8);
-    // (two rounds and more, the last one at most three quarters full: a launch of whole rounds -- the M2Det neck's 2 048- and 3 584-tile
-    // layers -- has no tail to even out and measured 0.1 ms slower per step with the fix-up traffic)
-    if (generic && generic_mode < 0 && (blocks < 2 * kStreamKWgs || blocks % kStreamKWgs == 0 || blocks % kStreamKWgs > 3 * kStreamKWgs / 4)) return false;
-    return nwg >= kStreamKMinWgs && blocks <= 16 * nwg;
+// request -> plan, as every entry point makes it: the deterministic flag and the knobs as they are at this call
+static ConvPlan plan_group(const ConvProblem* probs, int count, ConvForm form, ConvSplit split = kSplitNone, bool ws = false, bool vtab = false,
+                           int ws_wgs = kStreamKWgs) {
+    PlanRequest rq{};
+    rq.form = form; rq.vtab = vtab; rq.ws = ws; rq.ws_wgs = ws_wgs; rq.split = split;
+    rq.det = deterministic();
+    const char* f = (form == kFormGeneric && split == kSplitConv && !rq.det) ? conv_knob(K_CONV_FORCE) : nullptr;   // (ssdk_conv2d_fwd alone)
+    if (f && !(sscanf(f, "%d,%d", &rq.force_nb, &rq.force_ks) == 2 && rq.force_nb > 0 && rq.force_ks > 0)) rq.force_nb = rq.force_ks = 0;
+    rq.knobs = read_plan_knobs(probs, count, form, vtab, ws, split);
+    return plan_launch(probs, count, rq);
 }
 static unsigned g_streamk_epoch = 0;   // (a launch counter: tells this launch's flags from an earlier launch's in the same workspace)
 // A stream-K owner that gave up on a parked partner says so in a word of pinned, device-visible HOST memory (one per process, allocated
@@ -3033,175 +2938,68 @@ static unsigned* streamk_host_err_word(hipStream_t s) {
     return g_sk_host_err;
 }
 
-static int launch_group(ConvProblem* probs, int count, bool mirror, hipStream_t s, bool generic = false, bool scatter = false, int* vtab = nullptr,
-                        const StreamKWs* skws = nullptr) {
-    bool vec4 = true, strided = false;
-    for (int i = 0; i < count; ++i) {
-        const ConvProblem& g = probs[i];
-        if (g.Cc % 4 || g.a_pstride % 4 || g.a_bstride % 4 || ((uintptr_t)g.a & 15) || ((uintptr_t)g.w0 & 15) || (g.w1 && ((uintptr_t)g.w1 & 15))) vec4 = false;
-        strided = strided || g.stride != 1;
-    }
-    // LDS-DMA kernel: 16-byte rows, whole 32-channel chunks, stride-1 taps when mirrored, all byte offsets below 2^31
-    bool dma = vec4 && !(mirror && strided) && !getenv("SSDK_CONV_NO_DMA");
-    for (int i = 0; i < count && dma; ++i) {
-        ConvProblem& g = probs[i];
-        const long long span_a = ((long long)g.B * g.a_bstride + (long long)(g.ksize + g.pad) * ((long long)g.Win + 1) * g.a_pstride) * 4;
-        const long long w0_bytes = (long long)g.n0 * (scatter ? 1 : g.ksize * g.ksize) * g.Cc * 4, w1_bytes = (long long)g.n1 * g.ksize * g.ksize * g.Cc * 4;
-        if (g.Cc % kBK || span_a >= (1LL << 31) - 4096 || w0_bytes >= (1LL << 31) - 4096 || w1_bytes >= (1LL << 31) - 4096) { dma = false; break; }
-        g.w0_bytes = (unsigned)w0_bytes;
-        g.w1_bytes = (unsigned)w1_bytes;
-    }
-    // 16-float K slices (3 workgroups per CU): opt-in experiment for the plain forward launch
-    const bool bk16 = dma && !mirror && !generic && !scatter && getenv("SSDK_CONV_BK16");
-    // 192-column workgroups (6 column tiles) for the plain forward launch: opt-in experiment
-    const bool tn6 = dma && !mirror && !generic && !scatter && !bk16 && getenv("SSDK_CONV_TN6");
-    for (int i = 0; i < count; ++i) {   // column space of the chosen kernel (see ConvProblem::n0_pad)
-        ConvProblem& g = probs[i];
-        g.n0_pad = (dma && g.n1 > 0) ? cdiv(g.n0, bk16 ? 16 : 8) * (bk16 ? 16 : 8) : g.n0;
-        g.tiles_n = cdiv(g.n0_pad + g.n1, 32);
-        g.half_last = (dma && !mirror && !scatter && !bk16 && !tn6 && !g.stats && half_tile_of(g.n0_pad + g.n1) && !getenv("SSDK_CONV_W8") &&
-                       !getenv("SSDK_CONV_NO_HALF_TILE")) ? 1 : 0;
-        if (!g.forced) {
-            g.n_blocks = cdiv(g.tiles_n, tn6 ? 6 : kMaxTN);
-            if (!vtab && (scatter || g.k_splits > 1)) narrow_for_atomics(g);
-        }
-    }
-    // A launch smaller than the chip, whatever its epilogue: halve the columns per workgroup while the workgroups still fit one per CU.
-    // A 128 x 128 x 32 slice is 1.7 us of MFMA on one CU, so the 1 x 1 data gradients of the pyramid tail (K = 128: 4 slices, 6 .. 100
-    // workgroups of 128 columns) spent 9 us in the K loop and 6.6 us storing four column tiles on a chip that was 60-98 % idle
-    // (tools/phase_conv.py bwd); at 32 columns a slice costs its DMA latency (~0.85 us) instead.  The column partition does not change
-    // any sum's order: same bits.
-    // (not for the heads' forward launch: its stream-K partition is sized from the 128-column blocks)
-    if (!vtab && !skws && !getenv("SSDK_CONV_NO_NARROW")) {
-        static const long long fill = []() { const char* e = getenv("SSDK_CONV_NARROW_TO"); const long long v = e ? atoll(e) : 0; return v > 0 ? v : 256LL; }();   // (measurement knob)
-        long long total = 0;
-        for (int i = 0; i < count; ++i) total += (long long)probs[i].m_tiles * probs[i].n_blocks * probs[i].k_splits;
-        for (bool again = true; again && total < fill;) {
-            again = false;
-            for (int i = 0; i < count; ++i) {
-                ConvProblem& g = probs[i];
-                if (g.forced || g.n_blocks >= g.tiles_n) continue;
-                const int nb = std::min(g.tiles_n, g.n_blocks * 2);
-                const long long grown = total + (long long)g.m_tiles * (nb - g.n_blocks) * g.k_splits;
-                if (grown > fill) continue;
-                g.n_blocks = nb;
-                total = grown;
-                again = true;
-            }
-        }
-    }
-    // 8-wave / 256-pixel tiling: measured 3 % (B=128) to 14 % (B=32) MORE cycles than two 4-wave workgroups per CU on the
-    // SSD-300 heads (one barrier stalls all eight waves of the CU at once) -- kept as an opt-in experiment only
-    bool w8 = false;
-    if (dma && !scatter && getenv("SSDK_CONV_W8")) {
-        long long blocks256 = 0;
-        for (int i = 0; i < count; ++i) blocks256 += (long long)probs[i].m_tiles256 * probs[i].n_blocks * probs[i].k_splits;
-        w8 = blocks256 >= 384;
-    }
+// Launches a plan: the problems in the plan's order, the tile-list build in front of a sparse launch, the stream-K state of a stream-K one.
+static int launch_plan(const ConvPlan& pl, hipStream_t s, int* vtab = nullptr, void* sk_workspace = nullptr) {
+    SSDK_REQUIRE(pl.error != kPlanVtabNeedsCounts, SSDK_E_INVALID, "launch_plan: a tile list needs device-side row counts and no split-K");
+    SSDK_REQUIRE(pl.error != kPlanScatterUnaligned, SSDK_E_UNSUPPORTED, "scatter dgrad needs 16-byte aligned rows");
     ConvGroup grp;
-    int order[kMaxProblems];
-    for (int i = 0; i < count; ++i) order[i] = i;
-    for (int i = 0; i < count; ++i)
-        for (int j = i + 1; j < count; ++j)
-            if (problem_block_work(probs[order[j]]) > problem_block_work(probs[order[i]])) { int t = order[i]; order[i] = order[j]; order[j] = t; }
-    int begin = 0;
-    for (int i = 0; i < count; ++i) {
-        ConvProblem& g = probs[order[i]];
-        g.block_begin = begin;
-        begin += cdiv(w8 ? g.m_tiles256 : g.m_tiles, 8) * 8 * g.n_blocks * g.k_splits;
-        grp.p[i] = g;
-    }
-    grp.count = count;
-    grp.total_blocks = begin;
+    for (int i = 0; i < pl.count; ++i) grp.p[i] = pl.p[pl.order[i]];
+    grp.count = pl.count;
+    grp.total_blocks = pl.total_blocks;
     grp.vtab = nullptr;
-    if (dma && w8) {
-        if (mirror) hipLaunchKernelGGL((igemm_dma_kernel<true, false, false, 8>), dim3(begin), dim3(512), 0, s, grp);
-        else if (generic) hipLaunchKernelGGL((igemm_dma_kernel<false, true, false, 8>), dim3(begin), dim3(512), 0, s, grp);
-        else hipLaunchKernelGGL((igemm_dma_kernel<false, false, false, 8>), dim3(begin), dim3(512), 0, s, grp);
-    } else if (dma && scatter && vtab) {
-        // sparse backward: only the row tiles that exist (listed on the device), walked by a fixed grid of 8 workgroups per CU
+    StreamK sk{};
+    if (pl.kernel == kDmaScatterVtab) {
         VtabArgs va{};
-        va.count = count;
+        va.count = pl.count;
         va.vtab = vtab;
-        for (int i = 0; i < count; ++i) {
+        for (int i = 0; i < pl.count; ++i) {
             const ConvProblem& g = grp.p[i];
             va.p[i].counts = g.row_count;
             va.p[i].mode = g.mode; va.p[i].want = g.want_mode; va.p[i].n_blocks = g.n_blocks;
-            SSDK_REQUIRE(va.p[i].counts && g.k_splits == 1, SSDK_E_INVALID, "launch_group: a tile list needs device-side row counts and no split-K");
         }
         hipLaunchKernelGGL(build_vtab_kernel, dim3(1), dim3(64), 0, s, va);
         SSDK_CHECK_LAUNCH("build_vtab_kernel");
         grp.vtab = vtab;
-        hipLaunchKernelGGL((igemm_dma_kernel<false, false, true, 4>), dim3(2048), dim3(kConvThreads), 0, s, grp);
-    } else if (dma && skws && !scatter && !bk16 && !tn6 && !getenv("SSDK_CONV_NO_STREAMK")) {
-        // stream-K only where it pays: a launch of a few rounds of whole tiles (its last round is then a large share of the time), and
-        // every range at least as long as the longest tile (a tile is cut at most once)
-        StreamK sk{};
-        sk.nwg = skws->nwg;
-        long long max_tile = 0;
-        for (int i = 0; i < count; ++i) {
-            const ConvProblem& g = grp.p[i];
-            const long long slices = (long long)g.ksize * g.ksize * (g.Cc / kBK);
-            sk.unit_begin[i] = sk.total_units;
-            sk.total_units += (long long)g.m_tiles * slices * (2 * g.tiles_n - g.half_last);
-            max_tile = std::max(max_tile, slices * cdiv(g.tiles_n, g.n_blocks));
-            if (g.k_splits != 1 || g.mode) sk.nwg = 0;
-        }
-        sk.unit_begin[count] = sk.total_units;
-        // Not for launches of many rounds (the tail is then a small share and whole tiles need no fix-up).  Otherwise as many workgroups as
-        // leave each a range of at least kStreamKMinRange units (24 K slices of a 128-column block): a tile longer than a range is cut
-        // several times and its owner adds all the parked parts.  Below 256 workgroups the split-K path of the caller does as well (measured on ssd_mb2_voc).
-        if (sk.nwg > 0 && begin > 16 * sk.nwg) sk.nwg = 0;
-        const long long min_range = generic ? streamk_generic_min_range() : kStreamKMinRange;
-        if (sk.nwg > 0) sk.nwg = (int)std::min<long long>(sk.nwg, sk.total_units / (2 * min_range) / 8 * 8);   // (min_range counts whole tiles)
-        (void)max_tile;
-        const bool worth = sk.nwg >= kStreamKMinWgs;
-        if (worth) {
-            sk.partial = skws->partial;
-            sk.flags = skws->flags;
-            sk.timeouts = skws->flags + kStreamKWgs;   // (behind the flags of the largest launch)
-            sk.host_err = streamk_host_err_word(s);
-            sk.epoch = __atomic_add_fetch(&g_streamk_epoch, 1u, __ATOMIC_RELAXED);
-            if (sk.epoch == 0) sk.epoch = __atomic_add_fetch(&g_streamk_epoch, 1u, __ATOMIC_RELAXED);   // (0 is what a fresh workspace holds)
-            if (mirror) hipLaunchKernelGGL(igemm_streamk_kernel<true>, dim3(sk.nwg), dim3(kConvThreads), 0, s, grp, sk);
-            else hipLaunchKernelGGL(igemm_streamk_kernel<false>, dim3(sk.nwg), dim3(kConvThreads), 0, s, grp, sk);
-        } else if (mirror) {
-            hipLaunchKernelGGL((igemm_dma_kernel<true, false, false, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        } else if (generic) {
-            hipLaunchKernelGGL((igemm_dma_kernel<false, true, false, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        } else {
-            hipLaunchKernelGGL((igemm_dma_kernel<false, false, false, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        }
-    } else if (dma) {
-        // every workgroup of the launch owns ONE 32-column tile (the launches narrowed above, the atomic-epilogue launches of the small
-        // maps): the three-stage instantiation -- its K loop does not wait for a DMA issued one slice earlier but two
-        bool one_tile = !bk16 && !tn6 && !getenv("SSDK_CONV_NO_3STAGE");
-        for (int i = 0; i < count && one_tile; ++i) one_tile = grp.p[i].n_blocks == grp.p[i].tiles_n && !grp.p[i].half_last;
-        if (one_tile && scatter) hipLaunchKernelGGL((igemm_dma_kernel<false, false, true, 4, 32, 1>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (one_tile && mirror) hipLaunchKernelGGL((igemm_dma_kernel<true, false, false, 4, 32, 1>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (one_tile && generic) hipLaunchKernelGGL((igemm_dma_kernel<false, true, false, 4, 32, 1>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (scatter) hipLaunchKernelGGL((igemm_dma_kernel<false, false, true, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (mirror) hipLaunchKernelGGL((igemm_dma_kernel<true, false, false, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (generic) hipLaunchKernelGGL((igemm_dma_kernel<false, true, false, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (bk16) hipLaunchKernelGGL((igemm_dma_kernel<false, false, false, 4, 16>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else if (tn6) hipLaunchKernelGGL((igemm_dma_kernel<false, false, false, 4, 32, 6>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else hipLaunchKernelGGL((igemm_dma_kernel<false, false, false, 4>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-    } else if (scatter) {
-        SSDK_REQUIRE(vec4, SSDK_E_UNSUPPORTED, "scatter dgrad needs 16-byte aligned rows");
-        hipLaunchKernelGGL((igemm_fwd_kernel<4, false, false, false, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-    } else if (mirror && strided) {
-        if (vec4) hipLaunchKernelGGL((igemm_fwd_kernel<4, true, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else hipLaunchKernelGGL((igemm_fwd_kernel<1, true, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-    } else if (mirror) {
-        if (vec4) hipLaunchKernelGGL((igemm_fwd_kernel<4, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else hipLaunchKernelGGL((igemm_fwd_kernel<1, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-    } else if (generic) {  // same code, separate instantiation: profiles list the extras/tower convs apart from the heads
-        if (vec4) hipLaunchKernelGGL((igemm_fwd_kernel<4, false, false, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else hipLaunchKernelGGL((igemm_fwd_kernel<1, false, false, true>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-    } else {
-        if (vec4) hipLaunchKernelGGL((igemm_fwd_kernel<4, false>), dim3(begin), dim3(kConvThreads), 0, s, grp);
-        else hipLaunchKernelGGL((igemm_fwd_kernel<1, false>), dim3(begin), dim3(kConvThreads), 0, s, grp);
+    } else if (pl.streamk_wgs) {
+        const StreamKWs ws = carve_streamk(sk_workspace);
+        sk.nwg = pl.streamk_wgs;
+        for (int i = 0; i <= pl.count; ++i) sk.unit_begin[i] = pl.unit_begin[i];
+        sk.total_units = pl.unit_begin[pl.count];
+        sk.partial = ws.partial;
+        sk.flags = ws.flags;
+        sk.timeouts = ws.flags + kStreamKWgs;   // (behind the flags of the largest launch)
+        sk.host_err = streamk_host_err_word(s);
+        sk.epoch = __atomic_add_fetch(&g_streamk_epoch, 1u, __ATOMIC_RELAXED);
+        if (sk.epoch == 0) sk.epoch = __atomic_add_fetch(&g_streamk_epoch, 1u, __ATOMIC_RELAXED);   // (0 is what a fresh workspace holds)
     }
+#define SSDK_CONV_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(pl.grid), dim3(pl.threads), 0, s, grp)
+    switch (pl.kernel) {
+        case kDmaW8Mirror: SSDK_CONV_LAUNCH(igemm_dma_kernel<true, false, false, 8>); break;
+        case kDmaW8Generic: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, true, false, 8>); break;
+        case kDmaW8Plain: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, false, 8>); break;
+        case kDmaScatterVtab: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, true, 4>); break;
+        case kStreamKMirror: hipLaunchKernelGGL(igemm_streamk_kernel<true>, dim3(pl.grid), dim3(pl.threads), 0, s, grp, sk); break;
+        case kStreamK: hipLaunchKernelGGL(igemm_streamk_kernel<false>, dim3(pl.grid), dim3(pl.threads), 0, s, grp, sk); break;
+        case kDmaScatterOne: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, true, 4, 32, 1>); break;
+        case kDmaMirrorOne: SSDK_CONV_LAUNCH(igemm_dma_kernel<true, false, false, 4, 32, 1>); break;
+        case kDmaGenericOne: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, true, false, 4, 32, 1>); break;
+        case kDmaScatter: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, true, 4>); break;
+        case kDmaMirror: SSDK_CONV_LAUNCH(igemm_dma_kernel<true, false, false, 4>); break;
+        case kDmaGeneric: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, true, false, 4>); break;
+        case kDmaBk16: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, false, 4, 16>); break;
+        case kDmaTn6: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, false, 4, 32, 6>); break;
+        case kDmaPlain: SSDK_CONV_LAUNCH(igemm_dma_kernel<false, false, false, 4>); break;
+        case kStagedScatter4: SSDK_CONV_LAUNCH(igemm_fwd_kernel<4, false, false, false, true>); break;
+        case kStagedMirrorStrided4: SSDK_CONV_LAUNCH(igemm_fwd_kernel<4, true, true>); break;
+        case kStagedMirrorStrided1: SSDK_CONV_LAUNCH(igemm_fwd_kernel<1, true, true>); break;
+        case kStagedMirror4: SSDK_CONV_LAUNCH(igemm_fwd_kernel<4, true>); break;
+        case kStagedMirror1: SSDK_CONV_LAUNCH(igemm_fwd_kernel<1, true>); break;
+        case kStagedGeneric4: SSDK_CONV_LAUNCH(igemm_fwd_kernel<4, false, false, true>); break;   // (same code as the plain one, separate instantiation: profiles list the extras/tower convs apart from the heads)
+        case kStagedGeneric1: SSDK_CONV_LAUNCH(igemm_fwd_kernel<1, false, false, true>); break;
+        case kStagedPlain4: SSDK_CONV_LAUNCH(igemm_fwd_kernel<4, false>); break;
+        case kStagedPlain1: SSDK_CONV_LAUNCH(igemm_fwd_kernel<1, false>); break;
+    }
+#undef SSDK_CONV_LAUNCH
     SSDK_CHECK_LAUNCH("igemm_fwd_kernel");
     return SSDK_OK;
 }
@@ -3260,63 +3058,46 @@ extern "C" int ssdk_heads_fwd_ex(const ssdk_head_level* levels, int n_levels, in
         g.o0 = scores + lv.scores_offset; g.ob0 = scores_batch_stride; g.os0 = lv.n_score;
         g.o1 = lv.n_loc ? locs + lv.locs_offset : nullptr; g.ob1 = locs_batch_stride; g.os1 = lv.n_loc;
         g.relu = 0;
-        finish_problem(g);
         probs[i] = g;
     }
-    // Small batches: a level has a handful of row tiles, each with a K chain of 9 * Cin / 32 slices (1.5 us apiece) -- ssd_mb2_voc at batch
-    // 2 spent 534 us in 24 workgroups.  While the launch is too small for stream-K (at most one workgroup per slot), the K slices of such
-    // a level are divided over several workgroups that add into the zeroed outputs, like the pyramid tail's convolutions.
-    long long blocks = 0;
-    for (int i = 0; i < n_levels; ++i) blocks += (long long)cdiv(probs[i].m_tiles, 8) * 8 * probs[i].n_blocks;
-    bool dma_ok = true;   // (what launch_group asks of its LDS-DMA kernel; stream-K is a form of it)
-    for (int i = 0; i < n_levels; ++i) dma_ok = dma_ok && probs[i].Cc % kBK == 0;
     const bool have_ws = workspace && workspace_bytes >= ssdk_heads_fwd_workspace_bytes();
-    const bool streamk_takes_it = have_ws && dma_ok && streamk_would_take(probs, n_levels, false);
-    if (blocks <= kStreamKWgs && !streamk_takes_it && !getenv("SSDK_HEADS_NO_SPLITK")) {
-        bool any = false;
-        for (int i = 0; i < n_levels; ++i) any = maybe_split_k(probs[i]) || any;
-        if (any) {
-            ZeroList zl;
-            for (int which = 0; which < 2; ++which) {
-                // the split levels' segments of one image's row, merged where they touch (levels are usually laid out back to back)
-                long long off[kMaxProblems], len[kMaxProblems];
-                int ns = 0;
-                for (int i = 0; i < n_levels; ++i) {
-                    const ssdk_head_level& lv = levels[i];
-                    const long long n = (long long)lv.h * lv.w * (which ? lv.n_loc : lv.n_score);
-                    if (probs[i].k_splits > 1 && n > 0) { off[ns] = which ? lv.locs_offset : lv.scores_offset; len[ns] = n; ++ns; }
-                }
-                for (int a = 0; a < ns; ++a)
-                    for (int b = a + 1; b < ns; ++b)
-                        if (off[b] < off[a]) { std::swap(off[a], off[b]); std::swap(len[a], len[b]); }
-                int m = 0;
-                for (int a = 0; a < ns; ++a) {
-                    if (m && off[m - 1] + len[m - 1] == off[a]) len[m - 1] += len[a];
-                    else { off[m] = off[a]; len[m] = len[a]; ++m; }
-                }
-                float* const base = which ? locs : scores;
-                const long long stride = which ? locs_batch_stride : scores_batch_stride;
-                for (int b = 0; b < batch; ++b)
-                    for (int a = 0; a < m; ++a) {
-                        if (zl.a.count == kMaxZero) { const int rc = zl.launch((hipStream_t)stream); if (rc) return rc; }
-                        zl.add(base + (long long)b * stride + off[a], (size_t)len[a]);
-                    }
+    // a caller that runs other kernels BESIDE this launch (the pyramid tail on a second stream) leaves them LDS slots: the persistent
+    // workgroups of the stream-K form otherwise hold every slot of the chip until the launch ends
+    const int ws_wgs = max_workgroups > 0 ? std::max(kStreamKMinWgs, std::min(kStreamKWgs, max_workgroups / 8 * 8)) : kStreamKWgs;
+    const ConvPlan pl = plan_group(probs, n_levels, kFormPlain, kSplitHeads, have_ws, false, ws_wgs);
+    bool any = false;
+    for (int i = 0; i < n_levels; ++i) any = any || pl.zero_first[i];
+    if (any) {
+        ZeroList zl;
+        for (int which = 0; which < 2; ++which) {
+            // the split levels' segments of one image's row, merged where they touch (levels are usually laid out back to back)
+            long long off[kMaxProblems], len[kMaxProblems];
+            int ns = 0;
+            for (int i = 0; i < n_levels; ++i) {
+                const ssdk_head_level& lv = levels[i];
+                const long long n = (long long)lv.h * lv.w * (which ? lv.n_loc : lv.n_score);
+                if (pl.zero_first[i] && n > 0) { off[ns] = which ? lv.locs_offset : lv.scores_offset; len[ns] = n; ++ns; }
             }
-            const int rc = zl.launch((hipStream_t)stream);
-            if (rc) return rc;
+            for (int a = 0; a < ns; ++a)
+                for (int b = a + 1; b < ns; ++b)
+                    if (off[b] < off[a]) { std::swap(off[a], off[b]); std::swap(len[a], len[b]); }
+            int m = 0;
+            for (int a = 0; a < ns; ++a) {
+                if (m && off[m - 1] + len[m - 1] == off[a]) len[m - 1] += len[a];
+                else { off[m] = off[a]; len[m] = len[a]; ++m; }
+            }
+            float* const base = which ? locs : scores;
+            const long long stride = which ? locs_batch_stride : scores_batch_stride;
+            for (int b = 0; b < batch; ++b)
+                for (int a = 0; a < m; ++a) {
+                    if (zl.a.count == kMaxZero) { const int rc = zl.launch((hipStream_t)stream); if (rc) return rc; }
+                    zl.add(base + (long long)b * stride + off[a], (size_t)len[a]);
+                }
         }
+        const int rc = zl.launch((hipStream_t)stream);
+        if (rc) return rc;
     }
-    StreamKWs sk{};
-    if (workspace && workspace_bytes >= ssdk_heads_fwd_workspace_bytes()) {
-        Carver c(workspace);
-        sk.partial = c.take<float>((size_t)(kStreamKWgs + 1) * (4 * kMaxTN * 4 * 64 * 4));
-        sk.flags = c.take<unsigned>((size_t)kStreamKWgs + 2);
-        sk.nwg = kStreamKWgs;
-        // a caller that runs other kernels BESIDE this launch (the pyramid tail on a second stream) leaves them LDS slots: the persistent
-        // workgroups of the stream-K form otherwise hold every slot of the chip until the launch ends
-        if (max_workgroups > 0) sk.nwg = std::max(kStreamKMinWgs, std::min(kStreamKWgs, max_workgroups / 8 * 8));
-    }
-    return launch_group(probs, n_levels, false, (hipStream_t)stream, false, false, nullptr, sk.nwg ? &sk : nullptr);
+    return launch_plan(pl, (hipStream_t)stream, nullptr, workspace);
 }
 
 extern "C" int ssdk_streamk_poisoned(void) {
@@ -3330,9 +3111,7 @@ extern "C" int ssdk_streamk_reset(void* workspace, size_t workspace_bytes, void*
     SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_heads_fwd_workspace_bytes(), SSDK_E_WORKSPACE,
                  "ssdk_streamk_reset: the workspace of ssdk_heads_fwd (ssdk_heads_fwd_workspace_bytes() bytes) is required");
     SSDK_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-    Carver c(workspace);
-    c.take<float>((size_t)(kStreamKWgs + 1) * (4 * kMaxTN * 4 * 64 * 4));
-    unsigned* flags = c.take<unsigned>((size_t)kStreamKWgs + 2);
+    unsigned* flags = carve_streamk(workspace).flags;
     SSDK_CHECK_HIP(zero_async(flags, ((size_t)kStreamKWgs + 2) * sizeof(unsigned), (hipStream_t)stream));
     SSDK_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     if (g_sk_host_err) *static_cast<volatile unsigned*>(g_sk_host_err) = 0u;
@@ -3342,8 +3121,7 @@ extern "C" int ssdk_streamk_reset(void* workspace, size_t workspace_bytes, void*
 // (fault injection is honoured only when the process asked for it: SSDK_ENABLE_FAULT_INJECTION=1 in the environment -- the two device
 // globals it sets are read by every stream-K launch)
 extern "C" int ssdk_debug_streamk_fault(int drop_workgroup, unsigned spin_limit) {
-    const char* en = getenv("SSDK_ENABLE_FAULT_INJECTION");
-    SSDK_REQUIRE(en && atoi(en) != 0, SSDK_E_UNSUPPORTED, "ssdk_debug_streamk_fault: fault injection is off (set SSDK_ENABLE_FAULT_INJECTION=1: tests only)");
+    SSDK_REQUIRE(knob_nonzero(K_ENABLE_FAULT_INJECTION), SSDK_E_UNSUPPORTED, "ssdk_debug_streamk_fault: fault injection is off (set SSDK_ENABLE_FAULT_INJECTION=1: tests only)");
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_sk_drop_wg), &drop_workgroup, sizeof(int));
     if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_sk_spin_limit), &spin_limit, sizeof(unsigned));
     SSDK_REQUIRE(e == hipSuccess, (int)e, "ssdk_debug_streamk_fault: %s", hipGetErrorString(e));
@@ -3353,9 +3131,7 @@ extern "C" int ssdk_debug_streamk_fault(int drop_workgroup, unsigned spin_limit)
 extern "C" int ssdk_heads_fwd_timeouts(const void* workspace, size_t workspace_bytes, void* stream, unsigned* timeouts_host) {
     SSDK_REQUIRE(workspace && timeouts_host && workspace_bytes >= ssdk_heads_fwd_workspace_bytes(), SSDK_E_WORKSPACE,
                  "ssdk_heads_fwd_timeouts: workspace of ssdk_heads_fwd_workspace_bytes() bytes and a host word are required");
-    Carver c(const_cast<void*>(workspace));
-    c.take<float>((size_t)(kStreamKWgs + 1) * (4 * kMaxTN * 4 * 64 * 4));
-    const unsigned* flags = c.take<unsigned>((size_t)kStreamKWgs + 2);
+    const unsigned* flags = carve_streamk(const_cast<void*>(workspace)).flags;
     SSDK_CHECK_HIP(hipMemcpyAsync(timeouts_host, flags + kStreamKWgs, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
     SSDK_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     if (g_sk_host_err && *static_cast<volatile unsigned*>(g_sk_host_err) && *timeouts_host == 0u) *timeouts_host = 1u;   // (another workspace's)
@@ -3418,7 +3194,7 @@ extern "C" int ssdk_heads_fwd_fast(const ssdk_head_level* levels, int n_levels, 
     }
     hipLaunchKernelGGL(split_weights_kernel, dim3(split_blocks), dim3(256), 0, s, sg);
     SSDK_CHECK_LAUNCH("split_weights_kernel");
-    // grouped launch, problems ordered by decreasing work per workgroup (as launch_group)
+    // grouped launch, problems ordered by decreasing work per workgroup (as plan_launch)
     int order[kMaxProblems];
     for (int i = 0; i < n_levels; ++i) order[i] = i;
     for (int i = 0; i < n_levels; ++i)
@@ -3564,7 +3340,7 @@ static int launch_fast_group(ConvProblem* probs, FastProblem* fps, int n, SplitG
 }
 // fast mode: launches below this many FLOPs stay fp32 (SSDK_FAST_MIN_FLOPS: tests set 0 to put small shapes through the bf16 kernel)
 static double fast_min_flops() {
-    const char* e = getenv("SSDK_FAST_MIN_FLOPS");
+    const char* e = conv_knob(K_FAST_MIN_FLOPS);
     return e ? atof(e) : 1.0e9;
 }
 // can a stride-1 data gradient -- the forward-form convolution of `a` [batch][h][w][ch] with a ksize x ksize kernel, `wrows` weight
@@ -3646,7 +3422,7 @@ static HeadsBwdWs carve_heads_bwd(void* ws, const ssdk_head_level* levels, int n
 // atomic tile, so never fewer than 2 slices per split.
 // picks the LDS-DMA kernel when every problem of the group qualifies (16-byte rows, operands below 2 GiB, pixel count below 2^24)
 static int launch_wgrad(WgradGroup& wg, hipStream_t s, bool fast = false, bool rows32 = false) {
-    bool dma = !getenv("SSDK_CONV_NO_DMA");
+    bool dma = !knob_set(K_CONV_NO_DMA);
     for (int i = 0; i < wg.count && dma; ++i) {
         WgradProblem& g = wg.p[i];
         const long long rows = g.seg_count ? g.seg_cap : (long long)g.B * g.Hout * g.Wout;
@@ -3748,11 +3524,10 @@ static void size_wgrad_splits(WgradGroup& wg, int n, int density_div) {
 // order_out[old index] = new index of the problem in wg.p.  Groups of one problem keep the per-problem rule, and so does deterministic
 // mode: there the split count fixes the order of the sums, and a layer's weight gradient must come out with the same bits whether it
 // is computed alone or deferred into a group (eager step against the graphed hot path, tests/test_end_to_end_gpu.py).
-static int wgrad_knob(const char* name, int dflt) { const char* e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 ? v : dflt; }
 static void size_wgrad_group(WgradGroup& wg, int n, int* order_out = nullptr) {
-    static const bool launch_wide = getenv("SSDK_WGRAD_PER_PROBLEM") == nullptr;   // (measurement knob: the per-problem rule everywhere)
-    static const int budget = wgrad_knob("SSDK_WGRAD_BUDGET", 512);                // workgroups of the launch (measurement knob)
-    static const int min_chain = wgrad_knob("SSDK_WGRAD_MIN_CHAIN", 8);            // shortest K chain in slices (measurement knob)
+    static const bool launch_wide = !knob_set(K_WGRAD_PER_PROBLEM);   // (measurement knob: the per-problem rule everywhere)
+    static const int budget = knob_positive(K_WGRAD_BUDGET, 512);                // workgroups of the launch (measurement knob)
+    static const int min_chain = knob_positive(K_WGRAD_MIN_CHAIN, 8);            // shortest K chain in slices (measurement knob)
     for (int i = 0; i < n && order_out; ++i) order_out[i] = i;
     if (n <= 1 || !launch_wide || deterministic()) { size_wgrad_splits(wg, n, 1); return; }
     long long steps = 0;
@@ -3799,7 +3574,7 @@ static void size_wgrad_group(WgradGroup& wg, int n, int* order_out = nullptr) {
 // level's T buffer, else 0 = dense.  Both forms sum in an order fixed by the launch: no atomics, no zero-fill, the same bits on every run
 // and in a HIP-graph replay, whatever ssdk_set_deterministic says (it governs the legacy pipeline below and the generic convolutions).
 static int heads_t_div() {
-    static const int v = []() { const char* e = getenv("SSDK_HEADS_T_DIV"); const int d = e ? atoi(e) : 0; return d >= 1 ? d : 4; }();
+    static const int v = knob_positive(K_HEADS_T_DIV, 4);
     return v;
 }
 // rows of a level's T buffer: a quarter of its anchors (hard-negative mining marks ~4 %), never fewer than 4 096 (small maps always fit)
@@ -3808,8 +3583,8 @@ static inline long long t_rows_of(const ssdk_head_level& lv, int batch) {
     return std::min(all, std::max<long long>(4096, (all + heads_t_div() - 1) / heads_t_div()));
 }
 static bool ordered_heads_ok(const ssdk_head_level* levels, int n_levels, int batch) {
-    if (getenv("SSDK_CONV_NO_DMA") || getenv("SSDK_HEADS_BWD_LEGACY")) return false;
-    const char* f = getenv("SSDK_HEADS_BWD_MODE");
+    if (knob_set(K_CONV_NO_DMA) || knob_set(K_HEADS_BWD_LEGACY)) return false;
+    const char* f = conv_knob(K_HEADS_BWD_MODE);
     if (f && atoi(f) == 1) return false;   // (the pixel-row form exists in the legacy pipeline only)
     for (int i = 0; i < n_levels; ++i) {
         const ssdk_head_level& lv = levels[i];
@@ -3830,7 +3605,7 @@ static bool ordered_heads_ok(const ssdk_head_level* levels, int n_levels, int ba
 // `q < nq` branches -- the kernel is now instantiated per row-matrix width -- the same sweep read 224 / 160 / 208 / - / 173)
 static inline int anchor_wgrad_splits(const ssdk_head_level& lv, int batch) {
     const int slices = cdiv(cdiv(batch * lv.h * lv.w, 16), 32);
-    static const int per = []() { const char* e = getenv("SSDK_ANCHOR_WGRAD_SLICES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 64; }();   // (measurement knob)
+    static const int per = knob_positive(K_ANCHOR_WGRAD_SLICES, 64);   // (measurement knob)
     return std::max(1, std::min(8, cdiv(slices, per)));
 }
 struct OrderedWs {
@@ -3908,7 +3683,7 @@ static int heads_bwd_ordered(const ssdk_head_level* levels, int n_levels, int ba
     AnchorGroup ag{};
     ag.count = n_levels;
     {
-        const char* f = getenv("SSDK_HEADS_BWD_MODE");
+        const char* f = conv_knob(K_HEADS_BWD_MODE);
         ag.force = f ? atoi(f) : -1;
     }
     ag.acounts = w.acounts; ag.plan = w.plan; ag.mode = w.mode; ag.gtab = w.gtab; ag.zeros = w.zeros;
@@ -3931,7 +3706,7 @@ static int heads_bwd_ordered(const ssdk_head_level* levels, int n_levels, int ba
         // (a single head -- n_loc == 0 -- is covered when its columns start at a whole anchor: its locs_offset carries the anchor-type count)
         const bool covered = row_mask && lv.scores_offset % C == 0 && (LQ == 0 || lv.locs_offset == 4 * (lv.scores_offset / C)) &&
                              lv.scores_offset / C + (long long)hw * nb <= num_anchors;
-        if (covered && !getenv("SSDK_PACK_SCAN")) {
+        if (covered && !knob_set(K_PACK_SCAN)) {
             L.rmask = row_mask; L.a_total = num_anchors; L.a_off = (int)(lv.scores_offset / C);
         } else {
             L.rmask = w.imask[i]; L.a_total = hw * nb; L.a_off = 0;
@@ -3995,7 +3770,7 @@ static int heads_bwd_ordered(const ssdk_head_level* levels, int n_levels, int ba
         RowGemmGroup rg{};
         DxGroup dg{};
         rg.plan = w.plan; rg.acounts = w.acounts; rg.zeros = w.zeros;
-        { const char* e = getenv("SSDK_RG_PROBE"); rg.probe = e ? atoi(e) : 0; }
+        rg.probe = knob_int(K_RG_PROBE, 0);
         rg.count = n_levels;
         int dx_blocks = 0, kq = 1;
         bool any_dx = false;
@@ -4068,7 +3843,7 @@ static int heads_bwd_ordered(const ssdk_head_level* levels, int n_levels, int ba
             SSDK_CHECK_LAUNCH("transpose_group_kernel");
         }
         int rc = SSDK_OK;
-        if (n_rest) rc = launch_group(rest, n_rest, true, s);
+        if (n_rest) rc = launch_plan(plan_group(rest, n_rest, kFormMirror), s);
         if (!rc && n_fdg) rc = launch_fast_group(fdg, ffp, n_fdg, fsg, fsplit_blocks, s);
         if (rc) return rc;
     }
@@ -4205,7 +3980,7 @@ static int heads_bwd_impl(const ssdk_head_level* levels, int n_levels, int batch
         h_totals.v[i] = batch * levels[i].h * levels[i].w;
     }
     {   // test / experiment hook: SSDK_HEADS_BWD_MODE = 0 dense, 1 pixel-sparse, unset: by density (2 = anchor rows exists in the ordered pipeline only: by density here)
-        const char* f = getenv("SSDK_HEADS_BWD_MODE");
+        const char* f = conv_knob(K_HEADS_BWD_MODE);
         h_totals.force = f ? atoi(f) : -1;
         if (h_totals.force > 1) h_totals.force = -1;
     }
@@ -4332,10 +4107,10 @@ static int heads_bwd_impl(const ssdk_head_level* levels, int n_levels, int batch
             }
         }
         int rc = SSDK_OK;
-        if (n_rest) rc = launch_group(rest, n_rest, true, s);
+        if (n_rest) rc = launch_plan(plan_group(rest, n_rest, kFormMirror), s);
         if (!rc && n_fdg) rc = launch_fast_group(fdg, ffp, n_fdg, fsg, fsplit_blocks, s);
         if (rc) return rc;
-        if (!det) rc = launch_group(sparse, n_dgrad, false, s, false, true, w.vtab);
+        if (!det) rc = launch_plan(plan_group(sparse, n_dgrad, kFormScatter, kSplitNone, false, true), s, w.vtab);
         if (rc) return rc;
     }
 
@@ -4411,66 +4186,83 @@ static int check_conv(const char* fn, int batch, const ssdk_conv_desc& d) {
 }
 static inline int out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
 
+// ---- ssdk_conv_desc -> ConvProblem: the forward launch and the three data-gradient launches (ssdk_debug_conv2d_plan builds the same) ----
+static ConvProblem conv_fwd_problem(const ssdk_conv_desc& d, int batch) {
+    const int ho = out_dim(d.hin, d.ksize, d.stride, d.pad), wo = out_dim(d.win, d.ksize, d.stride, d.pad);
+    ConvProblem g{};
+    g.a = d.x; g.a_bstride = (long long)d.hin * d.win * d.cin; g.a_pstride = d.cin; g.Cc = d.cin;
+    g.B = batch; g.Hout = ho; g.Wout = wo; g.Hin = d.hin; g.Win = d.win; g.ksize = d.ksize; g.stride = d.stride; g.pad = d.pad;
+    g.w0 = d.w; g.w1 = nullptr; g.bias0 = d.bias; g.bias1 = nullptr; g.n0 = d.cout; g.n1 = 0;
+    g.o0 = d.y; g.ob0 = (long long)ho * wo * d.cout; g.os0 = d.cout; g.o1 = nullptr; g.ob1 = 0; g.os1 = 0;
+    g.relu = d.relu;
+    g.stats = d.stats;   // (known before the stream-K decision counts its units: a statistics epilogue rules the half-width last tile out; dropped by the plan for a split-K launch)
+    return g;
+}
+enum DgradKind { kDgradMirror, kDgradScatter, kDgradRows };
+// which data-gradient form a descriptor takes.  Strided: contribution rows + sum pass (ordered, no zero-fill) in deterministic mode; otherwise
+// the atomic scatter form, which measured 15-35 us faster per SSD-300 step (3.055 against 3.07-3.09 ms: the small maps' row GEMMs underfill
+// the chip); SSDK_CONV_STRIDED_ORDERED=1 takes the ordered form everywhere (measurement knob; the ordered form for the one layer whose T GEMM
+// fills the chip -- 3 x 3 / 2 256 -> 512 at 18 x 18, batch 32: 378 tiles -- and the scatter form for the rest: 2.921 against 2.920 ms
+// per step, medians of four interleaved runs: no gain, not kept).  Round 4's deterministic form -- the
+// output-stationary gather GEMM with three of four (pixel, tap) pairs masked -- cost 760 us per step where this costs 190.
+static DgradKind conv_dgrad_kind(const ssdk_conv_desc& d, bool det) {
+    static const bool strided_scatter = !knob_set(K_CONV_STRIDED_ORDERED);
+    return d.stride == 1 ? kDgradMirror : (det || !strided_scatter) ? kDgradRows : kDgradScatter;
+}
+// wd: the weights as the form reads them (mirror: [cin][tap][cout]; scatter, rows: [tap][cin][cout]); rows_t: the T buffer of the rows form
+static ConvProblem conv_dgrad_problem(const ssdk_conv_desc& d, int batch, DgradKind kind, const float* wd, float* rows_t) {
+    const int ho = out_dim(d.hin, d.ksize, d.stride, d.pad), wo = out_dim(d.win, d.ksize, d.stride, d.pad);
+    const int taps = d.ksize * d.ksize;
+    ConvProblem g{};
+    g.a = d.dy; g.a_bstride = (long long)ho * wo * d.cout; g.a_pstride = d.cout; g.Cc = d.cout;
+    g.B = batch; g.w0 = wd; g.n1 = 0;
+    if (kind == kDgradRows) {
+        // T = dy . W as a 1 x 1 GEMM over the output pixels (weights [tap][cin][cout]: rows tap * Cin + c, K = cout), then the sum pass
+        // (k_splits stays 1 -- whole K chains: a split would add into T with atomics; the plan may narrow the column blocks)
+        g.Hout = ho; g.Wout = wo; g.Hin = ho; g.Win = wo; g.ksize = 1; g.stride = 1; g.pad = 0;
+        g.n0 = taps * d.cin;
+        g.o0 = rows_t; g.ob0 = (long long)ho * wo * taps * d.cin; g.os0 = taps * d.cin;
+    } else if (kind == kDgradMirror) {
+        // output stationary: rows are INPUT pixels, A = dy [ho*wo][cout] with mirrored taps, W = wd [cin][taps*cout]
+        g.Hout = d.hin; g.Wout = d.win; g.Hin = ho; g.Win = wo; g.ksize = d.ksize; g.stride = 1; g.pad = d.pad;
+        g.n0 = d.cin;
+        g.o0 = d.dx; g.ob0 = (long long)d.hin * d.win * d.cin; g.os0 = d.cin;
+    } else {
+        // strided: input stationary.  T[out pixel][tap*cin + c] = dy[out pixel][:] . W[:, tap, c], scatter-added into
+        // dx at (yo*stride - pad + ky, xo*stride - pad + kx): no multiply is spent on (pixel, tap) pairs that do not exist
+        g.Hout = ho; g.Wout = wo; g.Hin = d.hin; g.Win = d.win; g.ksize = d.ksize; g.stride = d.stride; g.pad = d.pad;
+        g.n0 = taps * d.cin; g.sc_cin = d.cin;
+        g.o0 = d.dx; g.ob0 = (long long)d.hin * d.win * d.cin; g.os0 = d.cin;
+    }
+    finish_problem(g);   // (m_tiles: the fast mode's launch reads it)
+    return g;
+}
+
 extern "C" int ssdk_conv2d_fwd_ws(const ssdk_conv_desc* descs, int n, int batch, void* workspace, size_t workspace_bytes, void* stream) {
     SSDK_REQUIRE(descs && n > 0 && n <= kMaxProblems, SSDK_E_INVALID, "ssdk_conv2d_fwd: n=%d (1..%d)", n, kMaxProblems);
     SSDK_REQUIRE(!g_sk_host_err || *static_cast<volatile unsigned*>(g_sk_host_err) == 0u, SSDK_E_STREAMK_TIMEOUT,
                  "ssdk_conv2d_fwd: an earlier stream-K launch of this process gave up waiting for a parked partial tile -- see ssdk_heads_fwd_timeouts");
     ConvProblem probs[kMaxProblems];
-    ZeroList zl;
     for (int i = 0; i < n; ++i) {
         const ssdk_conv_desc& d = descs[i];
         int rc = check_conv("ssdk_conv2d_fwd", batch, d);
         if (rc) return rc;
         SSDK_REQUIRE(d.y, SSDK_E_INVALID, "ssdk_conv2d_fwd: null output");
-        const int ho = out_dim(d.hin, d.ksize, d.stride, d.pad), wo = out_dim(d.win, d.ksize, d.stride, d.pad);
-        ConvProblem g{};
-        g.a = d.x; g.a_bstride = (long long)d.hin * d.win * d.cin; g.a_pstride = d.cin; g.Cc = d.cin;
-        g.B = batch; g.Hout = ho; g.Wout = wo; g.Hin = d.hin; g.Win = d.win; g.ksize = d.ksize; g.stride = d.stride; g.pad = d.pad;
-        g.w0 = d.w; g.w1 = nullptr; g.bias0 = d.bias; g.bias1 = nullptr; g.n0 = d.cout; g.n1 = 0;
-        g.o0 = d.y; g.ob0 = (long long)ho * wo * d.cout; g.os0 = d.cout; g.o1 = nullptr; g.ob1 = 0; g.os1 = 0;
-        g.relu = d.relu;
         if (d.stats)
             SSDK_REQUIRE(d.cout % 4 == 0 && ((uintptr_t)d.y & 15) == 0, SSDK_E_UNSUPPORTED, "ssdk_conv2d_fwd: stats need cout %% 4 == 0 and a 16-byte aligned output");
-        g.stats = d.stats;   // (known before the stream-K decision counts its units: a statistics epilogue rules the half-width last tile out; dropped again below for a split-K launch)
-        finish_problem(g);
-        probs[i] = g;
+        probs[i] = conv_fwd_problem(d, batch);
     }
-    // One or two rounds of whole tiles on 256 CUs (the big layers of a pyramid tail): stream-K over all the launch's K slices instead of
-    // splitting K with an atomic epilogue into a zeroed output -- no zero-fill launch, no atomics, BatchNorm statistics still in the epilogue
-    const bool have_ws = workspace && workspace_bytes >= ssdk_heads_fwd_workspace_bytes();
-    const bool streamk = have_ws && streamk_would_take(probs, n, true);
-    for (int i = 0; i < n; ++i) {
-        const ssdk_conv_desc& d = descs[i];
-        ConvProblem& g = probs[i];
-        const int ho = g.Hout, wo = g.Wout;
-        bool split = !streamk && maybe_split_k(g);
-        const char* f = deterministic() ? nullptr : getenv("SSDK_CONV_FORCE");
-        if (f) {   // measurement knob (tools/conv_decomp_sweep.py): "<column blocks>,<K splits>"
-            int nb = 0, ks = 0;
-            if (!streamk && sscanf(f, "%d,%d", &nb, &ks) == 2 && nb > 0 && ks > 0) {
-                g.n_blocks = std::min(nb, g.tiles_n);
-                g.k_splits = (g.relu || ks < 2) ? 1 : ks;
-                g.forced = 1;
-                split = g.k_splits > 1;
-            }
-        }
-        if (split) zl.add(d.y, (size_t)batch * ho * wo * d.cout);
-        if (split) g.stats = nullptr;   // (in the epilogue otherwise; a split-K output is only complete after the launch: a pass of its own below)
-    }
+    const ConvPlan pl = plan_group(probs, n, kFormGeneric, kSplitConv, workspace && workspace_bytes >= ssdk_heads_fwd_workspace_bytes());
+    ZeroList zl;
+    for (int i = 0; i < n; ++i)
+        if (pl.zero_first[i]) zl.add(descs[i].y, (size_t)batch * pl.p[i].Hout * pl.p[i].Wout * descs[i].cout);
     int rc = zl.launch((hipStream_t)stream);
     if (rc) return rc;
-    StreamKWs sk{};
-    if (streamk) {
-        Carver c(workspace);
-        sk.partial = c.take<float>((size_t)(kStreamKWgs + 1) * (4 * kMaxTN * 4 * 64 * 4));
-        sk.flags = c.take<unsigned>((size_t)kStreamKWgs + 2);
-        sk.nwg = kStreamKWgs;
-    }
-    rc = launch_group(probs, n, false, (hipStream_t)stream, true, false, nullptr, streamk ? &sk : nullptr);
+    rc = launch_plan(pl, (hipStream_t)stream, nullptr, workspace);
     if (rc) return rc;
     for (int i = 0; i < n; ++i) {
         const ssdk_conv_desc& d = descs[i];
-        if (!d.stats || probs[i].stats) continue;
+        if (!d.stats || pl.stats_in_epilogue(i)) continue;
         const long long rows = (long long)batch * out_dim(d.hin, d.ksize, d.stride, d.pad) * out_dim(d.win, d.ksize, d.stride, d.pad);
         rc = ssdk_batchnorm_stats_accumulate(d.y, rows, d.cout, d.stats, stream);
         if (rc) return rc;
@@ -4586,13 +4378,6 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
     int dgrad_desc[kMaxProblems];
     StridedDxGroup sdg{};
     int n_rowsT = 0, sd_blocks = 0;
-    // strided data gradients: contribution rows + sum pass (ordered, no zero-fill) in deterministic mode; otherwise the atomic scatter
-    // form, which measured 15-35 us faster per SSD-300 step (3.055 against 3.07-3.09 ms: the small maps' row GEMMs underfill the chip);
-    // SSDK_CONV_STRIDED_ORDERED=1 takes the ordered form everywhere (measurement knob; the ordered form for the one layer whose T GEMM
-    // fills the chip -- 3 x 3 / 2 256 -> 512 at 18 x 18, batch 32: 378 tiles -- and the scatter form for the rest: 2.921 against 2.920 ms
-    // per step, medians of four interleaved runs: no gain, not kept).  Round 4's deterministic form -- the
-    // output-stationary gather GEMM with three of four (pixel, tap) pairs masked -- cost 760 us per step where this costs 190.
-    static const bool strided_scatter = getenv("SSDK_CONV_STRIDED_ORDERED") == nullptr;
     WgradGroup wg{};
     ZeroList zl{};
     int n_dgrad = 0, n_scat = 0, n_wgrad = 0;
@@ -4627,37 +4412,26 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
             wd = const_cast<float*>(d.w_t);
         }
         float* const rows_t = (d.dx && d.stride > 1) ? carve.take<float>((size_t)batch * ho * wo * taps * d.cin) : nullptr;
-        if (d.dx && d.stride != 1 && (det || !strided_scatter)) {
-            // T = dy . W as a 1 x 1 GEMM over the output pixels (weights [tap][cin][cout]: rows tap * Cin + c, K = cout), then the sum pass
-            if (!have_wt) {
+        const DgradKind kind = conv_dgrad_kind(d, det);
+        if (d.dx && !have_wt) {   // the weights as the form reads them
+            if (kind == kDgradMirror) {
+                hipLaunchKernelGGL(transpose_taps_kernel, dim3(cdiv(d.cout, 32), cdiv(d.cin, 32), taps), dim3(256), 0, s, d.w, (const float*)nullptr,
+                                   d.cout, 0, d.cout, taps, d.cin, wd);
+                SSDK_CHECK_LAUNCH("transpose_taps_kernel");
+            } else {
                 hipLaunchKernelGGL(transpose_tapmajor_kernel, dim3(cdiv(d.cout, 32), cdiv(d.cin, 32), taps), dim3(256), 0, s, d.w, (const float*)nullptr,
                                    d.cout, 0, d.cout, taps, d.cin, wd);
                 SSDK_CHECK_LAUNCH("transpose_tapmajor_kernel");
             }
-            ConvProblem g{};
-            g.a = d.dy; g.a_bstride = (long long)ho * wo * d.cout; g.a_pstride = d.cout; g.Cc = d.cout;
-            g.B = batch; g.Hout = ho; g.Wout = wo; g.Hin = ho; g.Win = wo; g.ksize = 1; g.stride = 1; g.pad = 0;
-            g.w0 = wd; g.n0 = taps * d.cin; g.n1 = 0;
-            g.o0 = rows_t; g.ob0 = (long long)ho * wo * taps * d.cin; g.os0 = taps * d.cin;
-            finish_problem(g);   // (k_splits stays 1 -- whole K chains: a split would add into T with atomics; launch_group may narrow the column blocks)
-            rowsT[n_rowsT++] = g;
+        }
+        if (d.dx && kind == kDgradRows) {
+            rowsT[n_rowsT++] = conv_dgrad_problem(d, batch, kind, wd, rows_t);
             StridedDxJob& J = sdg.j[sdg.count++];
             J.T = rows_t; J.dx = d.dx; J.B = batch; J.hin = d.hin; J.win = d.win; J.cin = d.cin; J.ho = ho; J.wo = wo; J.ks = d.ksize; J.stride = d.stride; J.pad = d.pad;
             J.blk_begin = sd_blocks;
             sd_blocks += (int)(((long long)batch * d.hin * d.win * (d.cin / 4) + 255) / 256);
-        } else if (d.dx && d.stride == 1) {
-            // output stationary: rows are INPUT pixels, A = dy [ho*wo][cout] with mirrored taps, W = wd [cin][taps*cout]
-            if (!have_wt) {
-                hipLaunchKernelGGL(transpose_taps_kernel, dim3(cdiv(d.cout, 32), cdiv(d.cin, 32), taps), dim3(256), 0, s, d.w, (const float*)nullptr,
-                                   d.cout, 0, d.cout, taps, d.cin, wd);
-                SSDK_CHECK_LAUNCH("transpose_taps_kernel");
-            }
-            ConvProblem g{};
-            g.a = d.dy; g.a_bstride = (long long)ho * wo * d.cout; g.a_pstride = d.cout; g.Cc = d.cout;
-            g.B = batch; g.Hout = d.hin; g.Wout = d.win; g.Hin = ho; g.Win = wo; g.ksize = d.ksize; g.stride = 1; g.pad = d.pad;
-            g.w0 = wd; g.n0 = d.cin; g.n1 = 0;
-            g.o0 = d.dx; g.ob0 = (long long)d.hin * d.win * d.cin; g.os0 = d.cin;
-            finish_problem(g);
+        } else if (d.dx && kind == kDgradMirror) {
+            ConvProblem g = conv_dgrad_problem(d, batch, kind, wd, nullptr);
             __bf16* const plane_hi = fast ? carve.take<__bf16>((size_t)cdiv(d.cin, 32) * 32 * taps * d.cout) : nullptr;
             __bf16* const plane_mid = fast ? carve.take<__bf16>((size_t)cdiv(d.cin, 32) * 32 * taps * d.cout) : nullptr;
             // (at least ~1 GFLOP: below that the split of the weights costs more than the bf16 MFMAs save -- the same bound ops.conv2d applies to the forward)
@@ -4681,25 +4455,12 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
                 fsrc[n_fdg] = wd;
                 fdg[n_fdg++] = g;
             } else {
-                dgrad_desc[n_dgrad] = i;   // (a K split of the small maps is decided below, once the launch is known not to take stream-K)
+                dgrad_desc[n_dgrad] = i;   // (a K split of the small maps is decided by the plan below, once the launch is known not to take stream-K)
                 dgrad[n_dgrad++] = g;
             }
         } else if (d.dx) {
-            // strided: input stationary.  T[out pixel][tap*cin + c] = dy[out pixel][:] . W[:, tap, c], scatter-added into
-            // dx at (yo*stride - pad + ky, xo*stride - pad + kx): no multiply is spent on (pixel, tap) pairs that do not exist
-            if (!have_wt) {
-                hipLaunchKernelGGL(transpose_tapmajor_kernel, dim3(cdiv(d.cout, 32), cdiv(d.cin, 32), taps), dim3(256), 0, s, d.w, (const float*)nullptr,
-                                   d.cout, 0, d.cout, taps, d.cin, wd);
-                SSDK_CHECK_LAUNCH("transpose_tapmajor_kernel");
-            }
             zl.add(d.dx, (size_t)batch * d.hin * d.win * d.cin);
-            ConvProblem g{};
-            g.a = d.dy; g.a_bstride = (long long)ho * wo * d.cout; g.a_pstride = d.cout; g.Cc = d.cout;
-            g.B = batch; g.Hout = ho; g.Wout = wo; g.Hin = d.hin; g.Win = d.win; g.ksize = d.ksize; g.stride = d.stride; g.pad = d.pad;
-            g.w0 = wd; g.n0 = taps * d.cin; g.n1 = 0; g.sc_cin = d.cin;
-            g.o0 = d.dx; g.ob0 = (long long)d.hin * d.win * d.cin; g.os0 = d.cin;
-            finish_problem(g);
-            scat[n_scat++] = g;
+            scat[n_scat++] = conv_dgrad_problem(d, batch, kind, wd, nullptr);
         }
         wg_of[i] = -1;
         if (d.dw) {
@@ -4727,10 +4488,11 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
     // stride-1 data gradients: a few rounds of whole tiles whose last round is partly filled (the RetinaNet towers: 2 688 tiles on 512 slots)
     // run in stream-K form, as the forward launch of the same layers -- with the caller's stream-K state (the workspace of ssdk_heads_fwd /
     // ssdk_conv2d_fwd_ws); otherwise the small maps split K (one long chain per tile: K = taps * cout) with atomics into a zeroed dx
-    const bool dgrad_sk = n_dgrad && sk_workspace && sk_workspace_bytes >= ssdk_heads_fwd_workspace_bytes() && streamk_would_take(dgrad, n_dgrad, true, true);
-    for (int q = 0; q < n_dgrad && !dgrad_sk; ++q) {
+    ConvPlan dgrad_plan;
+    if (n_dgrad) dgrad_plan = plan_group(dgrad, n_dgrad, kFormMirror, kSplitConv, sk_workspace && sk_workspace_bytes >= ssdk_heads_fwd_workspace_bytes());
+    for (int q = 0; q < n_dgrad; ++q) {
         const ssdk_conv_desc& d = descs[dgrad_desc[q]];
-        if (maybe_split_k(dgrad[q])) zl.add(d.dx, (size_t)batch * d.hin * d.win * d.cin);
+        if (dgrad_plan.zero_first[q]) zl.add(d.dx, (size_t)batch * d.hin * d.win * d.cin);
     }
     int rc = zl.launch(s);
     if (rc) return rc;
@@ -4763,23 +4525,15 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
         SSDK_CHECK_LAUNCH("colsum_kernel");
     }
     if (n_dgrad) {
-        StreamKWs sk{};
-        const bool use_sk = dgrad_sk;
-        if (use_sk) {
-            Carver c(sk_workspace);
-            sk.partial = c.take<float>((size_t)(kStreamKWgs + 1) * (4 * kMaxTN * 4 * 64 * 4));
-            sk.flags = c.take<unsigned>((size_t)kStreamKWgs + 2);
-            sk.nwg = kStreamKWgs;
-        }
-        rc = launch_group(dgrad, n_dgrad, true, s, use_sk, false, nullptr, use_sk ? &sk : nullptr);
+        rc = launch_plan(dgrad_plan, s, nullptr, sk_workspace);
         if (rc) return rc;
     }
     if (n_scat) {
-        rc = launch_group(scat, n_scat, false, s, false, true);
+        rc = launch_plan(plan_group(scat, n_scat, kFormScatter), s);
         if (rc) return rc;
     }
     if (n_rowsT) {
-        rc = launch_group(rowsT, n_rowsT, false, s, true);
+        rc = launch_plan(plan_group(rowsT, n_rowsT, kFormGeneric), s);
         if (rc) return rc;
         hipLaunchKernelGGL(strided_dx_kernel, dim3(sd_blocks), dim3(256), 0, s, sdg);
         SSDK_CHECK_LAUNCH("strided_dx_kernel");
@@ -4809,6 +4563,55 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
         }
         rc = rl.launch(s);
         if (rc) return rc;
+    }
+    return SSDK_OK;
+}
+
+
+// Host-only query: the launches ssdk_conv2d_fwd_ws (direction 0) / the data-gradient part of ssdk_conv2d_bwd(_sk) (direction 1) would make
+// for these descriptors NOW -- the same problems, request, knobs and plan_launch as the real call; no device, no dereferenced pointer.
+extern "C" int ssdk_debug_conv2d_plan(const ssdk_conv_desc* descs, int n, int batch, int direction, int have_workspace,
+                                      ssdk_conv_plan_launch* out, int max_launches, int* n_launches) {
+    SSDK_REQUIRE(descs && n > 0 && n <= kMaxProblems && out && n_launches && (direction == 0 || direction == 1), SSDK_E_INVALID,
+                 "ssdk_debug_conv2d_plan: n=%d (1..%d) direction=%d", n, kMaxProblems, direction);
+    ConvProblem probs[3][kMaxProblems];   // forward; or mirror, scatter, rows
+    int desc_of[3][kMaxProblems], count[3] = {0, 0, 0};
+    float* const fake = reinterpret_cast<float*>(uintptr_t(256));   // stands for the call's own (aligned) workspace buffers
+    const bool det = deterministic();
+    for (int i = 0; i < n; ++i) {
+        const ssdk_conv_desc& d = descs[i];
+        int rc = check_conv("ssdk_debug_conv2d_plan", batch, d);
+        if (rc) return rc;
+        int k = 0;
+        if (direction == 0) {
+            SSDK_REQUIRE(d.y, SSDK_E_INVALID, "ssdk_debug_conv2d_plan: null output");
+            probs[0][count[0]] = conv_fwd_problem(d, batch);
+        } else {
+            SSDK_REQUIRE(d.dy && d.cout % 4 == 0 && d.cin % 4 == 0 && ((uintptr_t)d.dy & 15) == 0 && ((uintptr_t)d.x & 15) == 0 && ((uintptr_t)d.w_t & 15) == 0,
+                         SSDK_E_UNSUPPORTED, "ssdk_debug_conv2d_plan: channels must be multiples of 4 and buffers 16-byte aligned");
+            if (!d.dx) continue;
+            const DgradKind kind = conv_dgrad_kind(d, det);
+            k = (int)kind;
+            probs[k][count[k]] = conv_dgrad_problem(d, batch, kind, d.w_t ? d.w_t : fake, fake);
+        }
+        desc_of[k][count[k]++] = i;
+    }
+    *n_launches = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!count[k]) continue;
+        SSDK_REQUIRE(*n_launches < max_launches, SSDK_E_INVALID, "ssdk_debug_conv2d_plan: more than %d launches", max_launches);
+        const ConvPlan pl = direction == 0  ? plan_group(probs[0], count[0], kFormGeneric, kSplitConv, have_workspace != 0)
+                            : k == kDgradMirror ? plan_group(probs[k], count[k], kFormMirror, kSplitConv, have_workspace != 0)
+                                                : plan_group(probs[k], count[k], k == kDgradScatter ? kFormScatter : kFormGeneric);
+        ssdk_conv_plan_launch& o = out[(*n_launches)++];
+        snprintf(o.kernel, sizeof(o.kernel), "%s%s", conv_kernel_name(pl.kernel), (direction == 1 && k == kDgradRows) ? " + strided_dx" : "");
+        o.grid = pl.grid;
+        o.count = pl.count;
+        for (int i = 0; i < pl.count; ++i) {
+            o.desc[i] = desc_of[k][i];
+            o.n_blocks[i] = pl.p[i].n_blocks; o.k_splits[i] = pl.p[i].k_splits; o.half_last[i] = pl.p[i].half_last;
+            o.block_begin[i] = pl.p[i].block_begin; o.blocks[i] = pl.blocks_of(i);
+        }
     }
     return SSDK_OK;
 }

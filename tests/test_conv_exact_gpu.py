@@ -11,13 +11,15 @@ accumulates.
 
 Each case's comment carries the arithmetic that puts it on its dispatch path.  Which kernel a case really ran on is shown by the kernel
 trace of this file, profiles/conv_exact_kernel_stats.md (DESIGN.md section 15 lists the instantiations seen there).  _plan() / _plan_dx()
-are a plain-Python SNAPSHOT of finish_problem, maybe_split_k_any, streamk_would_take and the narrowing / kernel choice of launch_group
-as they were when this file was written: they check the comments' arithmetic (tests/test_conv_reference.py runs them, no GPU needed),
-they do not consult the library, and they have to be re-derived when those rules change -- the trace is the proof, not the port."""
+ask the library itself: ssdk_debug_conv2d_plan builds the problems and the request of the real entry point and runs plan_launch
+(csrc/conv_plan.h), the one function every launch is planned by, without touching a device.  So the comments' arithmetic is checked against
+the rules that ship (tests/test_conv_reference.py runs the checks, no GPU needed), and the trace shows that the planned kernel is the
+one that ran."""
 import collections
 import contextlib
 import ctypes as C
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -186,123 +188,42 @@ def _exact_forward(s):
         cr.assert_exact(s.B * f['ho'] * f['wo'], ymax, ymax)
 
 
-# ---- the dispatch rules, in plain Python -------------------------------------------------------------------------------------------------
+# ---- the dispatch rules, asked of the library ---------------------------------------------------------------------------------------------
 
-def _half_tile(N):
-    return N % 32 != 0 and N % 32 <= 16
-
-
-def _problem(Cc, N, k, rows, relu=0, stats=0):
-    tiles_n = _cdiv(N, 32)
-    return dict(Cc=Cc, N=N, k=k, relu=relu, stats=stats, tiles_n=tiles_n, n_blocks=_cdiv(tiles_n, 4), m_tiles=_cdiv(rows, 128), k_splits=1, forced=0)
-
-
-def _split_k(g, det=False):
-    """maybe_split_k / maybe_split_k_any."""
-    t = dict(g)
-    blocks = _cdiv(t['m_tiles'], 8) * 8 * t['n_blocks']
-    slices = t['k'] * t['k'] * _cdiv(t['Cc'], 32)
-
-    def done():
-        if not det or t['k_splits'] == 1:
-            g.update(t)
-        if det:
-            g['k_splits'] = 1
-    if t['relu'] or blocks >= 256 or slices < 9:
-        return done()
-    if t['tiles_n'] >= 4 and t['tiles_n'] % 2 == 0 and t['m_tiles'] * (t['tiles_n'] // 2) >= 256 and slices <= 32:
-        t['n_blocks'], t['forced'] = t['tiles_n'] // 2, 1
-        return done()
-    if t['m_tiles'] >= 3 and (t['m_tiles'] <= 8 or (t['m_tiles'] <= 32 and t['m_tiles'] * t['tiles_n'] <= 256)) and slices >= 32:
-        t['n_blocks'] = t['tiles_n']
-        ks = min(max(2, 256 // max(1, t['m_tiles'] * t['n_blocks'])), slices // 8)
-        if t['m_tiles'] > 8 and t['m_tiles'] * t['n_blocks'] * ks > 512:
-            ks = 512 // (t['m_tiles'] * t['n_blocks'])
-        if t['m_tiles'] > 8 and ks < 2:
-            t['forced'] = 1
-            return done()
-        if ks >= 2:
-            t['k_splits'], t['forced'] = ks, 1
-            return done()
-        t['n_blocks'] = _cdiv(t['tiles_n'], 4)
-    ks = min(_cdiv(512, blocks), slices // 4)
-    if ks >= 2:
-        t['k_splits'] = ks
-    return done()
-
-
-def _streamk_generic(gs):
-    """streamk_would_take for a generic forward launch with a workspace."""
-    units = blocks = 0
-    for g in gs:
-        if g['Cc'] % 32:
-            return False
-        half = 1 if (not g['stats'] and _half_tile(g['N'])) else 0
-        units += g['m_tiles'] * g['k'] * g['k'] * (g['Cc'] // 32) * (2 * g['tiles_n'] - half)
-        blocks += _cdiv(g['m_tiles'], 8) * 8 * _cdiv(g['tiles_n'], 4)
-    nwg = min(512, units // (2 * 24) // 8 * 8)
-    if blocks < 1024 or blocks % 512 == 0 or blocks % 512 > 384:
-        return False
-    return nwg >= 256 and blocks <= 16 * nwg
-
-
-def _launch(gs, mirror=False, generic=True, scatter=False, aligned=True, no_dma=False, streamk=False):
-    """launch_group: the kernel it picks, by name, after narrowing the column blocks of gs in place."""
-    vec4 = aligned and all(g['Cc'] % 4 == 0 for g in gs)
-    dma = vec4 and not no_dma and all(g['Cc'] % 32 == 0 for g in gs)
-    for g in gs:
-        g['half_last'] = 1 if (dma and not mirror and not scatter and not g['stats'] and _half_tile(g['N'])) else 0
-        if not g['forced']:
-            g['n_blocks'] = _cdiv(g['tiles_n'], 4)
-            if scatter or g['k_splits'] > 1:
-                while g['n_blocks'] < g['tiles_n'] and g['m_tiles'] * g['n_blocks'] * g['k_splits'] <= 256:
-                    g['n_blocks'] = min(g['tiles_n'], g['n_blocks'] * 2)
-    if not streamk:
-        total = sum(g['m_tiles'] * g['n_blocks'] * g['k_splits'] for g in gs)
-        again = True
-        while again and total < 256:
-            again = False
-            for g in gs:
-                if g['forced'] or g['n_blocks'] >= g['tiles_n']:
-                    continue
-                nb = min(g['tiles_n'], g['n_blocks'] * 2)
-                grown = total + g['m_tiles'] * (nb - g['n_blocks']) * g['k_splits']
-                if grown > 256:
-                    continue
-                g['n_blocks'], total, again = nb, grown, True
-    form = 'scatter' if scatter else 'mirror' if mirror else 'generic' if generic else 'plain'
-    if dma and streamk:
-        return 'streamk'
-    if dma:
-        one_tile = all(g['n_blocks'] == g['tiles_n'] and not g['half_last'] for g in gs)
-        return f'dma {form}' + (' one-tile' if one_tile else '')
-    return f'staged<{4 if vec4 else 1}> {form}'
+def _planned(specs, direction, with_ws=False, det=False, no_dma=False, aligned=True):
+    """ssdk_debug_conv2d_plan (host only: no device, the fake pointers are never read) on these Specs, under SSDK_CONV_NO_DMA and the
+    deterministic flag as given (both restored): the launches it reports."""
+    lib = _lib.lib()
+    descs = (_lib.ConvDesc * len(specs))()
+    for d, s in zip(descs, specs):
+        d.x, d.hin, d.win, d.cin = 4096 + (0 if aligned else 4), s.H, s.W, s.cin
+        d.w, d.bias, d.y, d.dy, d.dx = 4096, (4096 if s.bias else None), 4096, 4096, 4096
+        d.cout, d.ksize, d.stride, d.pad, d.relu, d.stats = s.cout, s.k, s.stride, s.pad, s.relu, (4096 if s.stats else None)
+    out, n = (_lib.ConvPlanLaunch * 3)(), C.c_int(0)
+    before = os.environ.pop('SSDK_CONV_NO_DMA', None)
+    try:
+        if no_dma:
+            os.environ['SSDK_CONV_NO_DMA'] = '1'
+        with _deterministic(det):
+            rc = lib.ssdk_debug_conv2d_plan(descs, len(specs), specs[0].B, direction, int(with_ws), out, 3, C.byref(n))
+    finally:
+        os.environ.pop('SSDK_CONV_NO_DMA', None)
+        if before is not None:
+            os.environ['SSDK_CONV_NO_DMA'] = before
+    assert rc == OK, (rc, _err())
+    return [out[i] for i in range(n.value)]
 
 
 def _plan(specs, with_ws=False, det=False, no_dma=False, aligned=True):
     """ssdk_conv2d_fwd_ws on these Specs: (kernel, [(column blocks, K splits, half tile)] per problem)."""
-    gs = [_problem(s.cin, s.cout, s.k, s.B * cr.out_dim(s.H, s.k, s.stride, s.pad) * cr.out_dim(s.W, s.k, s.stride, s.pad), s.relu, s.stats) for s in specs]
-    streamk = with_ws and _streamk_generic(gs)
-    if not streamk:
-        for g in gs:
-            _split_k(g, det)
-            if g['k_splits'] > 1:
-                g['stats'] = 0   # (a split output is complete only after the launch: the statistics are a pass of their own)
-    kernel = _launch(gs, aligned=aligned, no_dma=no_dma, streamk=streamk)
-    return kernel, [(g['n_blocks'], g['k_splits'], g['half_last']) for g in gs]
+    launch, = _planned(specs, 0, with_ws, det, no_dma, aligned)
+    return launch.kernel.decode(), [(launch.n_blocks[i], launch.k_splits[i], launch.half_last[i]) for i in range(launch.count)]
 
 
 def _plan_dx(s, det=False, no_dma=False):
     """The data-gradient launch of ssdk_conv2d_bwd for one Spec: (kernel, column blocks, K splits)."""
-    ho, wo = cr.out_dim(s.H, s.k, s.stride, s.pad), cr.out_dim(s.W, s.k, s.stride, s.pad)
-    if s.stride == 1:
-        g = _problem(s.cout, s.cin, s.k, s.B * s.H * s.W)
-        _split_k(g, det)
-        return _launch([g], mirror=True, generic=False, no_dma=no_dma), g['n_blocks'], g['k_splits']
-    g = _problem(s.cout, s.k * s.k * s.cin, 1, s.B * ho * wo)
-    if det:
-        return _launch([g], generic=True, no_dma=no_dma) + ' + strided_dx', g['n_blocks'], 1
-    return _launch([g], generic=False, scatter=True, no_dma=no_dma), g['n_blocks'], 1
+    launch, = _planned([s], 1, False, det, no_dma)
+    return launch.kernel.decode(), launch.n_blocks[0], launch.k_splits[0]
 
 
 # ---- ssdk_conv2d_fwd / _ws / _fast --------------------------------------------------------------------------------------------------------
@@ -424,7 +345,7 @@ DMA_CASES = {'a': CASE_A, 'b': CASE_B, 'c': CASE_C, 'd': CASE_D, 'e': CASE_E, 'f
 
 
 def check_forward_cases_land_on_their_paths():
-    """The arithmetic of the comments above, through the port of the dispatch rules."""
+    """The arithmetic of the comments above, against the library's own dispatch rules."""
     assert _plan([CASE_A]) == ('dma generic', [(2, 1, 0)])
     assert _plan([CASE_B]) == ('dma generic one-tile', [(2, 1, 0)])
     assert _plan([CASE_C]) == ('dma generic one-tile', [(2, 4, 0)])
@@ -505,7 +426,7 @@ def test_forward_forced_decompositions(name, force, monkeypatch):
     _run_forward([s._replace(stats=1, xr=(-1, 1), wr=(-1, 1), nnz=6)])
 
 
-# eight problems of different work (launch_group orders them by K chain x columns per workgroup, so not in descriptor order): 1 x 1 and
+# eight problems of different work (plan_launch orders them by K chain x columns per workgroup, so not in descriptor order): 1 x 1 and
 # 3 x 3, both strides, a 1 x 1 map, H != W, maps of fewer than 128 rows, rows that are no multiple of 32 or 128
 GROUP8 = [spec(32, 40, 1, 1, 0, 5, 3, W=7), spec(64, 64, 3, 1, 1, 13, 3), spec(32, 96, 3, 2, 1, 9, 3, W=12), spec(128, 32, 1, 2, 0, 7, 3),
           spec(64, 8, 3, 1, 1, 1, 3), spec(32, 160, 3, 1, 0, 6, 3, W=11), spec(96, 64, 3, 2, 2, 8, 3), spec(64, 64, 3, 1, 1, 5, 3, W=3, salt=7)]

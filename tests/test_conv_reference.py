@@ -144,8 +144,64 @@ def test_assert_exact_accepts_what_fp32_holds_and_refuses_the_rest():
 
 
 def test_exact_gpu_cases_land_on_the_paths_their_comments_derive():
-    """The arithmetic in the comments of tests/test_conv_exact_gpu.py, through that file's plain-Python snapshot of the dispatch rules
-    (pure host arithmetic: it belongs to the suite that runs without a GPU)."""
+    """The arithmetic in the comments of tests/test_conv_exact_gpu.py, against the dispatch rules of the built library
+    (ssdk_debug_conv2d_plan: pure host arithmetic, it belongs to the suite that runs without a GPU)."""
     import test_conv_exact_gpu as exact
     exact.check_forward_cases_land_on_their_paths()
     exact.check_backward_cases_land_on_their_paths()
+
+
+_CIN = (3, 6, 24, 32, 64, 128, 256, 512, 1024)
+_COUT = (4, 32, 36, 40, 48, 64, 104, 256, 512)
+_KSP = ((1, 1, 0), (3, 1, 1), (3, 2, 1))
+_HS = (1, 2, 3, 5, 8, 9, 10, 19, 20, 32, 38, 64, 129)
+_BS = (1, 2, 4, 8, 32)
+
+
+@pytest.mark.parametrize('direction', [0, 1])
+@pytest.mark.parametrize('count', [1, 3, 8])
+def test_launch_plans_are_well_formed(count, direction):
+    """Grouped requests through ssdk_debug_conv2d_plan (host only): in every planned launch the problems' block ranges are disjoint and
+    tile the grid, lie in non-increasing order of work per workgroup (problem_block_work of csrc/conv_plan.h), K is split only where
+    nothing forbids it (deterministic mode, a fused ReLU; the third reason, a tile list, exists in the heads' backward only) and the
+    half-width last tile is set only where the column space ends in 1..16 columns."""
+    import test_conv_exact_gpu as exact
+    cdiv = lambda a, b: -(-a // b)
+    rng = np.random.RandomState(17 * count + direction)
+    pick = lambda seq: seq[rng.randint(len(seq))]
+    cins = [c for c in _CIN if direction == 0 or c % 4 == 0]
+    for trial in range(48):
+        B, det, with_ws = pick(_BS), bool(trial & 1), bool(trial & 2)
+        specs = []
+        for _ in range(count):
+            k, stride, pad = pick(_KSP)
+            specs.append(exact.spec(pick(cins), pick(_COUT), k, stride, pad, pick(_HS), B, relu=int(rng.randint(2)), stats=int(rng.randint(2))))
+        launches = exact._planned(specs, direction, with_ws=with_ws, det=det)
+        assert sum(l.count for l in launches) == count and sorted(d for l in launches for d in l.desc[:l.count]) == list(range(count))
+        for l in launches:
+            kernel = l.kernel.decode()
+            work, ranges = {}, []
+            for i in range(l.count):
+                s = specs[l.desc[i]]
+                if direction == 0:
+                    Cc, N, taps = s.cin, s.cout, s.k * s.k
+                elif s.stride == 1:
+                    Cc, N, taps = s.cout, s.cin, s.k * s.k
+                else:   # scatter: the taps are columns; ordered rows: a 1 x 1 GEMM
+                    Cc, N, taps = s.cout, s.k * s.k * s.cin, (1 if 'strided_dx' in kernel else s.k * s.k)
+                tiles_n = cdiv(N, 32)
+                assert 1 <= l.n_blocks[i] <= tiles_n and l.k_splits[i] >= 1, (specs, kernel, i)
+                if det or (direction == 0 and s.relu) or 'streamk' in kernel:
+                    assert l.k_splits[i] == 1, (specs, kernel, i)
+                if l.half_last[i]:
+                    assert 1 <= N % 32 <= 16, (specs, kernel, i)
+                ranges.append((l.block_begin[i], l.blocks[i]))
+                work[l.block_begin[i]] = taps * cdiv(Cc, 32) * cdiv(tiles_n, l.n_blocks[i]) // l.k_splits[i]
+            ranges.sort()
+            end = 0
+            for begin, blocks in ranges:
+                assert begin == end and blocks > 0, (specs, kernel, ranges)
+                end += blocks
+            assert end == l.grid or 'streamk' in kernel, (specs, kernel, ranges, l.grid)
+            in_order = [work[b] for b, _ in ranges]
+            assert in_order == sorted(in_order, reverse=True), (specs, kernel, in_order)
