@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 120
+#define SSDK_VERSION 122
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -471,6 +471,9 @@ typedef struct ssdk_conv_desc {
                            output and of its squares are ADDED (the values stored, i.e. after bias and ReLU), [2 * cout] = rows: the
                            statistics half of the BatchNorm that follows (bf/modules/conv.py:33-35), taken in the GEMM epilogue when the
                            convolution is not split over K, else by a pass over the output; cout % 4 == 0 */
+    int dx_is_zero;     /* ssdk_conv2d_bwd: non-zero = dx already holds zeros (ssdk_batchnorm_bwd_chained_ex zero-filled it on this stream): when the
+                           data gradient takes the atomic scatter form (ssdk_conv2d_dx_form == 1) the library skips its own zero-fill of dx and
+                           adds into the buffer as it is; every other form overwrites dx and ignores the flag */
 } ssdk_conv_desc;
 
 /* n <= 8 convolutions (e.g. the five pyramid levels of one shared tower layer) in one grouped launch. */
@@ -520,6 +523,13 @@ typedef struct ssdk_conv_plan_launch {
 } ssdk_conv_plan_launch;
 int ssdk_debug_conv2d_plan(const ssdk_conv_desc* descs, int n, int batch, int direction, int have_workspace, ssdk_conv_plan_launch* out,
                            int max_launches, int* n_launches);
+/* Host only: the form the data gradient of `desc` takes in ssdk_conv2d_bwd under the process' deterministic flag and environment, the
+ * plan's own decision: 0 = stride-1 GEMM (dx overwritten, or zero-filled by the library when it splits K), 1 = strided atomic scatter (dx
+ * zero-filled, then added into), 2 = strided ordered rows + sum pass (dx overwritten).  Only stride is read. */
+int ssdk_conv2d_dx_form(const ssdk_conv_desc* desc);
+/* TEST HOOK, host only: out[0] = zero-fill launches (zero_many_kernel) this process has made in the convolution entry points, out[1] = the
+ * floats they covered. */
+int ssdk_debug_zero_fill_counts(unsigned long long* out);
 /* dx = y > 0 ? dy : 0 (n floats, n % 4 == 0). */
 int ssdk_relu_bwd(const float* y, const float* dy, long long n, float* dx, void* stream);
 
@@ -580,6 +590,19 @@ int ssdk_batchnorm_fwd_chained(const float* x, long long rows, int channels, con
 int ssdk_batchnorm_bwd_chained(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
                                const float* save_mean, const float* save_rstd, int relu, float* dx, float* dgamma, float* dbeta,
                                double* sums, double* zero_after, void* stream);
+/* TEST HOOK, host only (no device): the grid of the statistics launches behind ssdk_batchnorm_stats / _stats_accumulate / _bwd_stats and the
+ * composed entry points for a [rows][channels] map, decided by the code and the environment (SSDK_BN_ROWS, SSDK_BN_WGS, SSDK_BN_SLAB) the real
+ * call uses.  out[4] = rows per workgroup, row blocks, slab width in float4 columns (a power of two <= 64), slabs.  The launch has
+ * row blocks x slabs workgroups, slabs innermost: workgroup g takes rows [g / slabs * rows_per_workgroup, ...) and the float4 columns
+ * [s * slab, (s + 1) * slab), s = g % slabs, then s + slabs, ... while they exist (slabs == 1: whole rows).  Exactly `row blocks` workgroups
+ * add to any one address of `sums`. */
+int ssdk_debug_batchnorm_plan(long long rows, int channels, long long* out);
+/* ssdk_batchnorm_bwd_chained whose apply launch also zero-fills zero_also[0 .. zero_also_floats) -- any float count, 4-byte aligned start, a
+ * buffer nothing else touches during the call; the stores are spread over the launch's workgroups.  NULL or 0: exactly
+ * ssdk_batchnorm_bwd_chained.  Meant for the dx of the producing strided convolution (ssdk_conv_desc::dx_is_zero). */
+int ssdk_batchnorm_bwd_chained_ex(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
+                                  const float* save_mean, const float* save_rstd, int relu, float* dx, float* dgamma, float* dbeta,
+                                  double* sums, double* zero_after, float* zero_also, long long zero_also_floats, void* stream);
 /* The statistics half alone, ADDING into `sums` (no zero-fill; sums[2 * channels] = rows), and the apply half of the chained form for sums
  * that are already complete -- accumulated by the producing convolution's epilogue (ssdk_conv_desc::stats): conv -> BatchNorm then costs one
  * launch for the norm instead of two, and the statistics pass over the activation is gone (bf/modules/conv.py:30-36). */

@@ -106,6 +106,7 @@ _SIGNATURES = {
     'ssdk_conv2d_transpose_weights': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'ssdk_relu_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     'ssdk_batchnorm_workspace_bytes': (C.c_size_t, [C.c_int]),
+    'ssdk_debug_batchnorm_plan': (C.c_int, [C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]),
     'ssdk_batchnorm_fwd': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -123,6 +124,10 @@ _SIGNATURES = {
                                              C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ssdk_batchnorm_bwd_chained': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ssdk_batchnorm_bwd_chained_ex': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'ssdk_conv2d_dx_form': (C.c_int, [C.c_void_p]),
+    'ssdk_debug_zero_fill_counts': (C.c_int, [C.POINTER(C.c_ulonglong)]),
     'ssdk_batchnorm_stats_accumulate': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     'ssdk_batchnorm_apply_chained': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                                C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -197,7 +202,7 @@ class ConvDesc(C.Structure):
     _fields_ = [('x', C.c_void_p), ('hin', C.c_int), ('win', C.c_int), ('cin', C.c_int), ('w', C.c_void_p),
                 ('bias', C.c_void_p), ('cout', C.c_int), ('ksize', C.c_int), ('stride', C.c_int), ('pad', C.c_int),
                 ('relu', C.c_int), ('y', C.c_void_p), ('dy', C.c_void_p), ('dx', C.c_void_p), ('dw', C.c_void_p),
-                ('db', C.c_void_p), ('w_t', C.c_void_p), ('stats', C.c_void_p)]
+                ('db', C.c_void_p), ('w_t', C.c_void_p), ('stats', C.c_void_p), ('dx_is_zero', C.c_int)]
 
 
 class ConvPlanLaunch(C.Structure):

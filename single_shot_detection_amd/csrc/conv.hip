@@ -43,6 +43,7 @@
 #include <mutex>
 
 #include "common.h"
+#include <atomic>
 #include "conv_plan.h"
 
 namespace ssdk {
@@ -2805,6 +2806,7 @@ using namespace ssdk;
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
+static std::atomic<unsigned long long> g_zero_launches{0}, g_zero_floats{0};   // (ssdk_debug_zero_fill_counts)
 struct ZeroList {
     ZeroArgs a;
     bool overflow;   // more than kMaxZero buffers between two launches: a caller bug, reported by launch() (never dropped silently)
@@ -2827,6 +2829,8 @@ struct ZeroList {
         const unsigned gx = (unsigned)std::min<unsigned long long>(2048, std::max<unsigned long long>(32, want));
         hipLaunchKernelGGL(zero_many_kernel, dim3(gx, a.count), dim3(256), 0, s, a);
         SSDK_CHECK_LAUNCH("zero_many_kernel");
+        g_zero_launches += 1;
+        for (int i = 0; i < a.count; ++i) g_zero_floats += a.n[i];
         a.count = 0;
         return SSDK_OK;
     }
@@ -4209,6 +4213,16 @@ static DgradKind conv_dgrad_kind(const ssdk_conv_desc& d, bool det) {
     static const bool strided_scatter = !knob_set(K_CONV_STRIDED_ORDERED);
     return d.stride == 1 ? kDgradMirror : (det || !strided_scatter) ? kDgradRows : kDgradScatter;
 }
+extern "C" int ssdk_conv2d_dx_form(const ssdk_conv_desc* desc) {
+    SSDK_REQUIRE(desc && desc->stride >= 1, SSDK_E_INVALID, "ssdk_conv2d_dx_form: bad arguments");
+    const DgradKind k = conv_dgrad_kind(*desc, deterministic());
+    return k == kDgradMirror ? 0 : k == kDgradScatter ? 1 : 2;
+}
+extern "C" int ssdk_debug_zero_fill_counts(unsigned long long* out) {
+    SSDK_REQUIRE(out, SSDK_E_INVALID, "ssdk_debug_zero_fill_counts: null output");
+    out[0] = g_zero_launches.load(); out[1] = g_zero_floats.load();
+    return SSDK_OK;
+}
 // wd: the weights as the form reads them (mirror: [cin][tap][cout]; scatter, rows: [tap][cin][cout]); rows_t: the T buffer of the rows form
 static ConvProblem conv_dgrad_problem(const ssdk_conv_desc& d, int batch, DgradKind kind, const float* wd, float* rows_t) {
     const int ho = out_dim(d.hin, d.ksize, d.stride, d.pad), wo = out_dim(d.win, d.ksize, d.stride, d.pad);
@@ -4459,7 +4473,7 @@ static int conv2d_bwd_impl(const ssdk_conv_desc* descs, int n, int batch, int ac
                 dgrad[n_dgrad++] = g;
             }
         } else if (d.dx) {
-            zl.add(d.dx, (size_t)batch * d.hin * d.win * d.cin);
+            if (!d.dx_is_zero) zl.add(d.dx, (size_t)batch * d.hin * d.win * d.cin);   // (else: zero-filled by the consumer norm's backward apply launch)
             scat[n_scat++] = conv_dgrad_problem(d, batch, kind, wd, nullptr);
         }
         wg_of[i] = -1;

@@ -6,19 +6,23 @@
 // and updates running_mean / running_var (unbiased) with `momentum`; eval mode uses the running statistics.
 //
 // All three kernels are HBM-bound streams over a [rows = B*H*W][C] matrix (channels contiguous, so a wave reads whole
-// lines): bn_reduce_kernel accumulates two per-channel sums (64 rows per workgroup in registers, then one fp64 atomic
-// per channel), bn_apply_kernel turns them into mean / rstd itself (and updates the running statistics), bn_apply_kernel /
-// bn_bwd_apply_kernel are the elementwise passes with the ReLU fused.
+// lines): bn_reduce_kernel accumulates two per-channel sums -- a workgroup takes 64 or more rows x a slab of 16 float4 columns, a wave
+// instruction four consecutive rows of the slab, in registers, then one fp64 atomic per channel (bn_reduce_plan: the grid is row blocks x
+// column slabs) -- bn_apply_kernel turns them into mean / rstd itself (and updates the running statistics), bn_apply_kernel /
+// bn_bwd_apply_kernel are the elementwise passes with the ReLU fused; both carry the side job of zero-filling the layer's other `sums`
+// buffer, and bn_bwd_apply_kernel a second one, spread over its grid: zero-filling the dx of the producing strided convolution (zero_also).
 #include "common.h"
 
 namespace ssdk {
 
 constexpr int kBnRows = 64;
-// Rows per bn_reduce workgroup.  Measured over the SSD-300 tail (rocprofv3, all eight layers; SSDK_BN_ROWS overrides): 64 rows is the best
+// Rows per bn_reduce workgroup.  The figures of this paragraph and of the first one inside the function are those of the WHOLE-ROW form
+// (every workgroup owns every channel: SSDK_BN_SLAB=0 today); the column slabs' own sweep is the last paragraph inside the function.
+// Measured over the SSD-300 tail (rocprofv3, all eight layers; SSDK_BN_ROWS overrides): 64 rows is the best
 // single value (8.3 us per launch on average; 128: 10.0, 256: 14.3 -- fewer, longer chains of dependent loads; 32: 10.4, 16: 16.3 --
 // the big maps then queue 4x the same-address fp64 atomics per channel).  Picking 16 / 32 rows for the small maps only (2.7 - 2.9 us
 // against 4.1) did not move the step time beyond run-to-run noise and is not done.
-static inline int bn_rows_per_block(long long rows) {
+static inline int bn_rows_per_block(long long rows, bool slabs) {
     if (const char* e = getenv("SSDK_BN_ROWS")) return atoi(e);
     // Large maps (RetinaNet's 63 x 63 level at batch 32: 127 k rows): every workgroup ends with one fp64 atomic per channel and sum, all on
     // the same 2C addresses, and with 64 rows 1 984 workgroups queue there.  bn_reduce<0> per launch, averaged over the tower's five levels
@@ -27,37 +31,86 @@ static inline int bn_rows_per_block(long long rows) {
     // 384: 24.8, 256: 23.0, 192: 23.1 (backward statistics alike: 60.7 -> 28.9).  retina_rn50_500_coco step 52.97 -> 50.17 ms.
     // (round 4, tools/ab_step.sh SSDK_BN_WGS 256 128 64 on one box: M2Det 31.45 / 31.28 / 31.73 ms per step, RetinaNet 46.57 / 46.53 / 46.82, SSD-300
     // unchanged: 128 -- the mid-size maps of the M2Det neck, 16 k rows, spent ~20 of their 36 us in the 256-way atomics)
-    const long long target = getenv("SSDK_BN_WGS") ? atoll(getenv("SSDK_BN_WGS")) : 128;
+    // With column slabs (bn_reduce_plan) the workgroups of a launch are row blocks x slabs and the chain of a workgroup is 64 / slab times
+    // shorter, so the row blocks -- the adders per address -- can be fewer: 64 (tools/bn_slab_sweep.py, slab 16, 128 -> 64, us per forward /
+    // backward launch summed over the maps: SSD-300 tail 44.9 / 67.3 -> 41.3 / 63.5, M2Det neck 141 / 300 -> 122 / 287, RetinaNet tower 68 / 135
+    // -> 62 / 118; 256: 49.0 / 71.5, 183 / 339, 94 / 140).  Whole rows (SSDK_BN_SLAB=0) keep 128.
+    const long long target = getenv("SSDK_BN_WGS") ? atoll(getenv("SSDK_BN_WGS")) : (slabs ? 64 : 128);
     long long r = (rows + target - 1) / target;
     r = (r + 15) / 16 * 16;
-    return (int)(r < kBnRows ? kBnRows : (r > 4096 ? 4096 : r));
+    // ... and at least 128 rows per workgroup with slabs (two trips of a workgroup over its rows; same tool, BN_SWEEP_RULES=1, floors 64 / 128 /
+    // 256 at 64 row blocks: SSD-300 tail 45.6 / 69.6, 42.7 / 68.9, 46.0 / 68.6; M2Det neck 122.8 / 290.2, 118.3 / 286.8, 119.4 / 286.9; RetinaNet
+    // tower 63.5 / 123.1, 62.7 / 123.3, 61.1 / 122.0; 32, 48 and 96 row blocks are no better on any of the three).
+    const long long least = slabs ? 2 * kBnRows : kBnRows;
+    return (int)(r < least ? least : (r > 4096 ? 4096 : r));
+}
+
+// The grid of a bn_reduce launch: (row blocks) x (column slabs), flattened with the slabs innermost so that neighbouring workgroups read
+// neighbouring bytes.  A workgroup owns `slab` float4 columns (a power of two, at most 64) of its rows, and a wave instruction takes
+// 64 / slab consecutive rows of them.  With whole rows per workgroup (the form before: slabs == 1) a map of 256 or 512 channels gave a wave
+// instruction one row, a 64-row workgroup a chain of four dependent memory trips per 64 columns and the launch 41 - 108 workgroups on 256
+// CUs; with 16-column slabs the same launch has 4 - 8x the workgroups, each with a quarter (an eighth) of the bytes and of the chain.  The
+// number of workgroups that add to one address is the number of ROW blocks: the rows-per-workgroup rule above balances exactly that
+// contention against the chain length, and with the shorter chains it aims at 64 row blocks instead of 128.
+//   SSDK_BN_SLAB (read per call): 0 = whole rows per workgroup (the form before: the A side of a measurement on one binary), else the
+//   slab width in float4 columns, rounded up to a power of two and capped at 64.  Default 16: 256-byte row segments.
+//   C / 4 that the slab width does not divide (33 = 132 / 4, 224 = 896 / 4): the LAST SLAB IS NARROWER -- its spare lanes idle, as the
+//   spare lanes of the last 64 columns always did; falling back to whole rows would have kept the M2Det reducers (C = 896) out.
+//   C / 4 below the slab width: one slab of the next power of two (C / 4 = 12: 16 columns, 4 idle, four rows per instruction).
+struct BnReducePlan {
+    int rows_per_block, slab, slabs;   // slab: float4 columns per workgroup and trip; slabs: workgroups side by side over the columns
+    int fold64;                        // folds across lanes and waves in fp64 (every layout but the packed / whole-row forms of before)
+    long long row_blocks;
+};
+static inline int bn_pow2_at_least(int v) { int p = 1; while (p < v && p < 64) p <<= 1; return p; }
+static inline BnReducePlan bn_reduce_plan(long long rows, int C) {
+    BnReducePlan p;
+    const int C4 = C >> 2;
+    const char* e = getenv("SSDK_BN_SLAB");
+    const int want = e ? atoi(e) : 16;
+    p.rows_per_block = bn_rows_per_block(rows, want > 0);
+    if (p.rows_per_block < 1) p.rows_per_block = 1;
+    p.row_blocks = (rows + p.rows_per_block - 1) / p.rows_per_block;
+    if (want <= 0) {   // whole rows: one workgroup walks all columns, 64 at a time (a row of at most 32 that divides 64: packed)
+        p.slab = (C4 <= 32 && 64 % C4 == 0) ? C4 : 64;
+        p.slabs = 1;
+        p.fold64 = 0;
+    } else {
+        p.slab = bn_pow2_at_least(want < C4 ? want : C4);
+        p.slabs = (C4 + p.slab - 1) / p.slab;
+        p.fold64 = !(p.slabs == 1 && p.slab == C4);   // (one slab as wide as the row IS the packed form of before: its arithmetic, its bits)
+    }
+    return p;
 }
 
 // MODE 0: s0 = sum x, s1 = sum x^2.   MODE 1 (backward): s0 = sum dy', s1 = sum dy' * xhat, dy' = relu ? dy * (y > 0) : dy
-// Workgroup = 64 rows; wave w takes rows w, w+4, ...; lane l owns float4 columns l, l+64, ... (whole 1 KB lines per wave).
+// Workgroup = rows_per_block rows x one column slab (see bn_reduce_plan); lane l owns float4 column l % slab of the slab and row l / slab of
+// the 64 / slab consecutive rows a wave instruction takes; wave w takes row groups w, w+4, ...  The lanes that share a column are folded
+// with cross-lane adds, the four waves through LDS, and the workgroup ends with ONE atomic per channel and sum.
 // MODE 0 accumulates in fp64 from the first add on: the variance is E[x^2] - mean^2, and with fp32 partial sums a channel whose mean is
 // 100 standard deviations lost four digits of it ("BatchNorm statistics: conditioning").  The square of an fp32 value is exact
-// in fp64; the kernel streams from HBM and the fp64 adds hide behind the loads.  MODE 1 sums centred, scaled values and stays in fp32.
+// in fp64; the kernel streams from HBM and the fp64 adds hide behind the loads.  MODE 1 sums centred, scaled values: a lane's own chain of
+// adds stays in fp32; the folds across lanes and waves behind it are fp64 in the layouts the slabs introduce (fold64, see the fold below).
 template <typename T> struct bn_acc4 { T x, y, z, w; };
 template <int MODE>
 __global__ void __launch_bounds__(256) bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
-                                                        long long rows, int rows_per_block, int C, const float* __restrict__ mean,
-                                                        const float* __restrict__ rstd, int relu, double* __restrict__ sums) {
+                                                        long long rows, int rows_per_block, int C, int slab, int slabs, int fold64,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd, int relu,
+                                                        double* __restrict__ sums) {
     using acc_t = typename std::conditional<MODE == 0, double, float>::type;
     using acc4 = bn_acc4<acc_t>;
-    __shared__ acc4 s_part[2][4][64];   // (16 KB in MODE 0, 8 KB in MODE 1)
-    const long long r0 = (long long)blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+    __shared__ bn_acc4<double> s_part[2 * 4 * 64];   // (16 KB: [sum][wave][lane], fp64 or the accumulator's type)
+    const int my_slab = (int)(blockIdx.x % (unsigned)slabs);
+    const long long r0 = (long long)(blockIdx.x / (unsigned)slabs) * rows_per_block, r1 = min(rows, r0 + rows_per_block);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C4 = C >> 2;
-    // Rows of at most 32 float4 (C <= 128: the 128-channel smoothing layers of the M2Det neck, 48 of its 131 norms): a wave instruction
-    // takes 64 / C4 consecutive rows instead of one row on half (a quarter, ...) of its lanes; the lanes that share a column are folded
-    // with cross-lane adds at the end.
-    const bool packed = C4 <= 32 && (64 % C4) == 0;
-    const int rpw = packed ? 64 / C4 : 1;          // rows per wave instruction
-    const int sub = packed ? lane / C4 : 0;        // this lane's row inside them
+    const int rpw = 64 / slab;            // rows per wave instruction (slab is a power of two)
+    const int col = lane & (slab - 1);    // this lane's column inside the slab
+    const int sub = lane / slab;          // ... and its row inside the rpw rows
     if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = (double)rows;   // (slot 2C: the count behind the sums)
-    for (int cbase = 0; cbase < C4; cbase += 64) {
-        const int c4 = packed ? lane - sub * C4 : cbase + lane;
+    // (slabs == 1: this workgroup walks all the columns, `slab` at a time -- whole rows)
+    for (int cbase = my_slab * slab; cbase < C4; cbase += slabs * slab) {
+        const int c4 = cbase + col;
         acc4 a0 = {0, 0, 0, 0}, a1 = a0;
         if (c4 < C4) {
             float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), rs4 = m4;
@@ -101,22 +154,34 @@ __global__ void __launch_bounds__(256) bn_reduce_kernel(const float* __restrict_
                 }
             }
         }
-        if (packed) {   // (uniform) lanes c4, c4 + C4, c4 + 2 C4, ... hold the same column: fold them into lane c4
-            for (int d = C4; d < 64; d <<= 1) {
-                a0.x += __shfl_xor(a0.x, d, 64); a0.y += __shfl_xor(a0.y, d, 64); a0.z += __shfl_xor(a0.z, d, 64); a0.w += __shfl_xor(a0.w, d, 64);
-                a1.x += __shfl_xor(a1.x, d, 64); a1.y += __shfl_xor(a1.y, d, 64); a1.z += __shfl_xor(a1.z, d, 64); a1.w += __shfl_xor(a1.w, d, 64);
+        // (uniform) lanes col, col + slab, col + 2 slab, ... hold the same column: fold them into lane col, then the four waves through LDS.
+        // fold64 == 0 (the workgroup is the packed or the whole-row form of before: one slab as wide as the row, or SSDK_BN_SLAB=0): the folds
+        // are in the accumulator's type, fp32 in MODE 1, operation for operation what that form always did -- same bits.  fold64 != 0 (every
+        // layout the slabs introduce): the folds are fp64 in both modes (the conversion is exact), so MODE 1's fp32 rounding is that of a
+        // lane's own rows / (16 * rpw) adds and nothing else.  With fp32 folds the slab form, which folds 64 / slab lanes where the whole-row
+        // form folded none, missed the dx bar of tests/test_batchnorm_kernels_gpu.py on a channel that is zero in most rows (1.6 x the bar;
+        // tools/bn_fold_emulation.py reproduces both orders on the test's data).
+        auto fold = [&](auto tag) {
+            using F = decltype(tag);
+            using fold4 = bn_acc4<F>;
+            fold4* const part = reinterpret_cast<fold4*>(s_part);   // [2][4][64]
+            fold4 f0 = {(F)a0.x, (F)a0.y, (F)a0.z, (F)a0.w}, f1 = {(F)a1.x, (F)a1.y, (F)a1.z, (F)a1.w};
+            for (int d = slab; d < 64; d <<= 1) {
+                f0.x += __shfl_xor(f0.x, d, 64); f0.y += __shfl_xor(f0.y, d, 64); f0.z += __shfl_xor(f0.z, d, 64); f0.w += __shfl_xor(f0.w, d, 64);
+                f1.x += __shfl_xor(f1.x, d, 64); f1.y += __shfl_xor(f1.y, d, 64); f1.z += __shfl_xor(f1.z, d, 64); f1.w += __shfl_xor(f1.w, d, 64);
             }
-        }
-        __syncthreads();
-        s_part[0][wave][lane] = a0;
-        s_part[1][wave][lane] = a1;
-        __syncthreads();
-        if (wave < 2 && (packed ? lane < C4 : c4 < C4)) {  // wave 0 folds the s0 partials, wave 1 the s1 partials
-            acc4 t = s_part[wave][0][lane];
-            for (int w = 1; w < 4; ++w) { const acc4 u = s_part[wave][w][lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-            double* dst = sums + (size_t)wave * C + (size_t)(packed ? lane : c4) * 4;
-            atomicAdd(dst + 0, (double)t.x); atomicAdd(dst + 1, (double)t.y); atomicAdd(dst + 2, (double)t.z); atomicAdd(dst + 3, (double)t.w);
-        }
+            __syncthreads();
+            part[(0 * 4 + wave) * 64 + lane] = f0;
+            part[(1 * 4 + wave) * 64 + lane] = f1;
+            __syncthreads();
+            if (wave < 2 && lane < slab && c4 < C4) {  // wave 0 folds the s0 partials, wave 1 the s1 partials
+                fold4 t = part[(wave * 4 + 0) * 64 + lane];
+                for (int w = 1; w < 4; ++w) { const fold4 u = part[(wave * 4 + w) * 64 + lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+                double* dst = sums + (size_t)wave * C + (size_t)c4 * 4;
+                atomicAdd(dst + 0, (double)t.x); atomicAdd(dst + 1, (double)t.y); atomicAdd(dst + 2, (double)t.z); atomicAdd(dst + 3, (double)t.w);
+            }
+        };
+        if (fold64) fold(double{}); else fold(acc_t{});
     }
 }
 
@@ -211,7 +276,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ gamma, const double* __restrict__ sums,
                                                            const double* __restrict__ sums_local, int count_on_device, int relu, int training,
                                                            float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                           double* __restrict__ zero_after) {
+                                                           double* __restrict__ zero_after, float* __restrict__ zero_also, long long zero_also_n) {
     // relu bit 0: the norm's own fused ReLU (dy counts where y > 0); bit 1: the norm's INPUT is the output of a ReLU whose gradient is
     // taken here as well (dx = 0 where x <= 0: conv -> ReLU -> BatchNorm of the RetinaNet tower, the producing convolution then skips its
     // own ReLU-gradient pass)
@@ -220,6 +285,21 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restri
     const int C4 = C >> 2;
     if (zero_after && blockIdx.x == gridDim.x - 1)
         for (int c = threadIdx.x; c < 2 * C + 2; c += blockDim.x) zero_after[c] = 0.0;
+    // second side job: zero-fill zero_also[0 .. zero_also_n) -- the dx of the producing convolution when its data gradient is the atomic
+    // scatter form, a buffer nobody reads or writes during this launch.  Spread over the whole grid (megabytes from one workgroup would
+    // outlast the launch): float4 stores over the 16-byte aligned middle, the at most 3 + 3 floats around it by the last workgroup.
+    if (zero_also) {
+        long long head = (long long)(((16 - ((uintptr_t)zero_also & 15)) & 15) >> 2);
+        if (head > zero_also_n) head = zero_also_n;
+        const long long mid4 = (zero_also_n - head) >> 2, tail0 = head + 4 * mid4;
+        float4* const mid = reinterpret_cast<float4*>(zero_also + head);
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < mid4; i += (long long)gridDim.x * blockDim.x) mid[i] = z;
+        if (blockIdx.x == gridDim.x - 1) {
+            if ((long long)threadIdx.x < head) zero_also[threadIdx.x] = 0.0f;
+            if (tail0 + (long long)threadIdx.x < zero_also_n) zero_also[tail0 + threadIdx.x] = 0.0f;   // (at most 3 floats)
+        }
+    }
     const double inv_n = 1.0 / (count_on_device ? sums[2 * C] : (double)rows);
     // A thread's four channels stay the same over its grid-stride trips whenever the stride is a multiple of the row length (C / 4 divides
     // 256 * gridDim for every power-of-two C): their five per-channel constants are then loaded and converted ONCE.  (Per element they
@@ -290,6 +370,14 @@ using namespace ssdk;
 // is two fill kernels in the runtime, one for the 16-byte aligned part and one for the tail)
 extern "C" size_t ssdk_batchnorm_workspace_bytes(int channels) { return align_up(((size_t)2 * channels + 2) * sizeof(double), 256); }
 
+// TEST HOOK, host only: the grid the statistics launches (bn_reduce_kernel<0> and <1> alike) take for this map under the environment of the call
+extern "C" int ssdk_debug_batchnorm_plan(long long rows, int channels, long long* out) {
+    SSDK_REQUIRE(out && rows > 0 && channels > 0 && channels % 4 == 0, SSDK_E_INVALID, "ssdk_debug_batchnorm_plan: bad arguments (channels %% 4 == 0)");
+    const BnReducePlan p = bn_reduce_plan(rows, channels);
+    out[0] = p.rows_per_block; out[1] = p.row_blocks; out[2] = p.slab; out[3] = p.slabs;
+    return SSDK_OK;
+}
+
 // The composed entry points launch twice: everything either half would refuse is refused here, before the first launch.
 static int bn_fwd_check(const char* fn, const float* x, const float* y, const float* save_mean, const float* save_rstd, long long rows, int channels) {
     SSDK_REQUIRE(x && y && save_mean && save_rstd && rows > 0 && channels > 0, SSDK_E_INVALID, "%s: bad arguments", fn);
@@ -309,9 +397,11 @@ static int bn_stats(const float* x, long long rows, int channels, double* sums, 
     SSDK_REQUIRE(channels % 4 == 0 && ((uintptr_t)x & 15) == 0, SSDK_E_UNSUPPORTED, "ssdk_batchnorm_stats: channels %% 4 != 0 or x not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (zero_first) SSDK_CHECK_HIP(zero_async(sums, sizeof(double) * (2 * (size_t)channels + 2), s));
-    const int rpb = bn_rows_per_block(rows);
-    hipLaunchKernelGGL(bn_reduce_kernel<0>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, x, (const float*)nullptr,
-                       (const float*)nullptr, rows, rpb, channels, (const float*)nullptr, (const float*)nullptr, 0, sums);
+    const BnReducePlan p = bn_reduce_plan(rows, channels);
+    SSDK_REQUIRE(p.row_blocks * p.slabs < (1ll << 31), SSDK_E_UNSUPPORTED, "ssdk_batchnorm_stats: %lld row blocks x %d slabs exceed the grid", p.row_blocks, p.slabs);
+    hipLaunchKernelGGL(bn_reduce_kernel<0>, dim3((unsigned)(p.row_blocks * p.slabs)), dim3(256), 0, s, x, (const float*)nullptr,
+                       (const float*)nullptr, rows, p.rows_per_block, channels, p.slab, p.slabs, p.fold64, (const float*)nullptr, (const float*)nullptr, 0,
+                       sums);
     SSDK_CHECK_LAUNCH("bn_reduce_kernel");
     return SSDK_OK;
 }
@@ -408,9 +498,10 @@ static int bn_bwd_stats(const float* x, const float* y, const float* dy, long lo
                  "ssdk_batchnorm_bwd_stats: channels %% 4 != 0 or buffers not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (zero_first) SSDK_CHECK_HIP(zero_async(sums, sizeof(double) * (2 * (size_t)channels + 2), s));
-    const int rpb = bn_rows_per_block(rows);
-    hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, x, y, dy, rows, rpb, channels, save_mean,
-                       save_rstd, relu, sums);
+    const BnReducePlan p = bn_reduce_plan(rows, channels);
+    SSDK_REQUIRE(p.row_blocks * p.slabs < (1ll << 31), SSDK_E_UNSUPPORTED, "ssdk_batchnorm_bwd_stats: %lld row blocks x %d slabs exceed the grid", p.row_blocks, p.slabs);
+    hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)(p.row_blocks * p.slabs)), dim3(256), 0, s, x, y, dy, rows, p.rows_per_block, channels,
+                       p.slab, p.slabs, p.fold64, save_mean, save_rstd, relu, sums);
     SSDK_CHECK_LAUNCH("bn_reduce_kernel");
     return SSDK_OK;
 }
@@ -423,7 +514,7 @@ extern "C" int ssdk_batchnorm_bwd_stats(const float* x, const float* y, const fl
 static int bn_bwd_apply(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
                         const float* save_mean, const float* save_rstd, int relu, int training, const double* sums,
                         const double* sums_local, const double* total_rows, float* dx, float* dgamma, float* dbeta, double* zero_after,
-                        void* stream) {
+                        float* zero_also, long long zero_also_floats, void* stream) {
     SSDK_REQUIRE(x && dy && dx && sums && save_mean && save_rstd && rows > 0 && channels > 0 && (!(relu & 1) || y), SSDK_E_INVALID,
                  "ssdk_batchnorm_bwd_apply: bad arguments");
     SSDK_REQUIRE(channels % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)y) & 15) == 0, SSDK_E_UNSUPPORTED,
@@ -432,7 +523,7 @@ static int bn_bwd_apply(const float* x, const float* y, const float* dy, long lo
                  "ssdk_batchnorm_bwd_apply: total_rows must be the slot behind the sums (sums + 2 * channels) or NULL");
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(apply_blocks(rows * channels / 4, channels / 4)), dim3(256), 0, (hipStream_t)stream, x, y, dy, rows, channels,
                        save_mean, save_rstd, gamma, sums, sums_local ? sums_local : sums, total_rows ? 1 : 0, relu, training, dx, dgamma, dbeta,
-                       zero_after);
+                       zero_after, zero_also_floats > 0 ? zero_also : (float*)nullptr, zero_also_floats);
     SSDK_CHECK_LAUNCH("bn_bwd_apply_kernel");
     return SSDK_OK;
 }
@@ -442,19 +533,30 @@ extern "C" int ssdk_batchnorm_bwd_apply(const float* x, const float* y, const fl
                                         const double* sums_local, const double* total_rows, float* dx, float* dgamma, float* dbeta,
                                         void* stream) {
     return bn_bwd_apply(x, y, dy, rows, channels, gamma, save_mean, save_rstd, relu, training, sums, sums_local, total_rows, dx, dgamma, dbeta,
-                        nullptr, stream);
+                        nullptr, nullptr, 0, stream);
 }
 
 // backward of ssdk_batchnorm_fwd_chained: `sums` (zeroed by the forward's apply launch) takes the backward sums, `zero_after` -- the
-// layer's forward buffer -- is zero-filled for the next forward.
-extern "C" int ssdk_batchnorm_bwd_chained(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
-                                          const float* save_mean, const float* save_rstd, int relu, float* dx, float* dgamma, float* dbeta,
-                                          double* sums, double* zero_after, void* stream) {
+// layer's forward buffer -- is zero-filled for the next forward.  _ex: the apply launch also zero-fills zero_also[0 .. zero_also_floats)
+// (any float count, 4-byte aligned start; NULL or 0: none) -- the caller's next accumulation target, the producing convolution's dx.
+extern "C" int ssdk_batchnorm_bwd_chained_ex(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
+                                             const float* save_mean, const float* save_rstd, int relu, float* dx, float* dgamma, float* dbeta,
+                                             double* sums, double* zero_after, float* zero_also, long long zero_also_floats, void* stream) {
     SSDK_REQUIRE(sums && sums != zero_after && dx, SSDK_E_INVALID, "ssdk_batchnorm_bwd_chained: bad arguments");
+    SSDK_REQUIRE(zero_also_floats >= 0 && ((uintptr_t)zero_also & 3) == 0, SSDK_E_INVALID,
+                 "ssdk_batchnorm_bwd_chained_ex: zero_also must be 4-byte aligned, its float count not negative");
     if (const int bad = bn_bwd_check("ssdk_batchnorm_bwd_chained", x, y, dy, dx, save_mean, save_rstd, rows, channels, relu)) return bad;
     const int rc = bn_bwd_stats(x, y, dy, rows, channels, save_mean, save_rstd, relu, sums, false, stream);
     if (rc) return rc;
-    return bn_bwd_apply(x, y, dy, rows, channels, gamma, save_mean, save_rstd, relu, 1, sums, nullptr, nullptr, dx, dgamma, dbeta, zero_after, stream);
+    return bn_bwd_apply(x, y, dy, rows, channels, gamma, save_mean, save_rstd, relu, 1, sums, nullptr, nullptr, dx, dgamma, dbeta, zero_after, zero_also,
+                        zero_also_floats, stream);
+}
+
+extern "C" int ssdk_batchnorm_bwd_chained(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,
+                                          const float* save_mean, const float* save_rstd, int relu, float* dx, float* dgamma, float* dbeta,
+                                          double* sums, double* zero_after, void* stream) {
+    return ssdk_batchnorm_bwd_chained_ex(x, y, dy, rows, channels, gamma, save_mean, save_rstd, relu, dx, dgamma, dbeta, sums, zero_after, nullptr, 0,
+                                         stream);
 }
 
 extern "C" int ssdk_batchnorm_bwd(const float* x, const float* y, const float* dy, long long rows, int channels, const float* gamma,

@@ -28,11 +28,12 @@ def _fast_min_flops():
 
 
 class _ConvFn(torch.autograd.Function):
-    """apply(weight, bias, stride, pad, relu, stats, *xs) -> tuple of outputs; the n inputs share `weight` (one grouped launch).
-    stats: None, or one fp64 `sums` buffer address (or None) per input: the BatchNorm statistics of that output are accumulated into it."""
+    """apply(weight, bias, stride, pad, relu, stats, links, *xs) -> tuple of outputs; the n inputs share `weight` (one grouped launch).
+    stats: None, or one fp64 `sums` buffer address (or None) per input: the BatchNorm statistics of that output are accumulated into it.
+    links: None, or one _DxLink (or None) per input, shared with the norm that consumes that output (conv2d_batch_norm)."""
 
     @staticmethod
-    def forward(ctx, weight, bias, stride, pad, relu, stats, *xs):
+    def forward(ctx, weight, bias, stride, pad, relu, stats, links, *xs):
         lib = _lib.lib()
         _lib.require_cuda(weight, *xs)
         w = weight.float().contiguous(memory_format=torch.channels_last)
@@ -67,6 +68,10 @@ class _ConvFn(torch.autograd.Function):
         # its input is not positive, conv2d_batch_norm): the backward gets dy already masked and skips its own pass over it
         ctx.meta = (stride, pad, relu == 1, len(xs), bias is not None, tuple(tuple(y.shape) for y in ys))
         ctx.params = (weight, bias)   # leaves: their gradient-bucket slots (distributed.GradBucket) are looked up in the backward
+        ctx.links = links
+        for i, link in enumerate(links or ()):
+            if link is not None:
+                link.describe(xs[i], cout, k, stride, pad, ctx.needs_input_grad[7 + i])
         return tuple(ys)
 
     @staticmethod
@@ -104,23 +109,26 @@ class _ConvFn(torch.autograd.Function):
                 _lib.check(lib.ssdk_relu_bwd(_dp(ys[i]), _dp(dy), dy.numel(), _dp(g), stream), 'ssdk_relu_bwd')
                 dy = g
             keep.append(dy)
-            dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[6 + i] else None
+            # (a dx that the consumer norm's backward apply launch has zero-filled in this graph task, on this stream: _DxLink)
+            zeroed = ctx.links[i].take(x) if ctx.links and ctx.links[i] is not None and ctx.needs_input_grad[7 + i] else None
+            dx = zeroed if zeroed is not None else (torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[7 + i] else None)
             dxs.append(dx)
             d = arr[i]
             d.x, d.hin, d.win, d.cin = _dp(x), x.shape[2], x.shape[3], cin
             d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = _dp(w), None, cout, k, stride, pad, 0
             d.dy, d.dx, d.dw, d.db = _dp(dy), _dp(dx), _dp(dw), _dp(db)
             d.w_t = _dp(ctx.w_t)
+            d.dx_is_zero = int(zeroed is not None)
         if defer:
             # jobs belong to ONE autograd graph task: a backward pass that raised leaves its callbacks unrun and its jobs behind -- they are
             # dropped (never added into a later step's gradients), and the flush is queued once per task, not "when the list was empty"
             _queue_deferred_wgrad(dict(x=xs[0], dy=keep[0], w=w, weight=ctx.params[0] if need_w else None, bias=ctx.params[1] if need_b else None,
                                        stride=stride, pad=pad))
             if all(dx is None for dx in dxs):
-                return (None, None, None, None, None, None) + tuple(dxs)
+                return (None, None, None, None, None, None, None) + tuple(dxs)
         _conv2d_bwd(lib, arr, n, B, w.device, stream)
         _forget_transposed_weights(ctx.params[0])
-        return (dw, db, None, None, None, None) + tuple(dxs)
+        return (dw, db, None, None, None, None, None) + tuple(dxs)
 
 
 # stream-K for the generic convolutions: the library takes it for launches of two rounds of tiles and more (conv.hip streamk_would_take:
@@ -535,13 +543,14 @@ def _flush_jobs(jobs):
 def conv2d(xs, weight, bias=None, stride=1, padding=0, relu=False):
     """Conv2d on a list of maps that share the weights (one grouped GEMM launch); returns a list."""
     single = isinstance(xs, torch.Tensor)
-    out = _ConvFn.apply(weight, bias, int(stride), int(padding), bool(relu), None, *([xs] if single else list(xs)))
+    out = _ConvFn.apply(weight, bias, int(stride), int(padding), bool(relu), None, None, *([xs] if single else list(xs)))
     return out[0] if single else list(out)
 
 
 _NO_FUSED_STATS = bool(__import__('os').environ.get('SSDK_NO_FUSED_STATS'))   # (measurement knob)
 _NO_BN_CHAIN = bool(__import__('os').environ.get('SSDK_NO_BN_CHAIN'))         # (measurement knob: every norm call zero-fills a scratch workspace)
 _NO_RELU_BY_NORM = bool(__import__('os').environ.get('SSDK_NO_RELU_BY_NORM'))   # (measurement knob)
+_NO_DX_ZERO_BY_NORM = bool(__import__('os').environ.get('SSDK_NO_DX_ZERO_BY_NORM'))   # (measurement knob: the convolution zero-fills its own dx)
 fused_stats_calls = 0   # (norm layers whose forward statistics were handed to a convolution's epilogue; tests read it)
 
 
@@ -579,15 +588,56 @@ def conv2d_batch_norm(xs, weight, bias, stride, padding, bns, conv_relu=False, b
     # conv -> ReLU -> norm with every norm on this path: the norms' backward also takes the ReLU's gradient (dx = 0 where the norm's input
     # is not positive), and the convolution's backward skips its own pass over dy
     relu_by_norm = bool(conv_relu) and all(c is not None for c in chains) and not _NO_RELU_BY_NORM
-    ys = _ConvFn.apply(weight, bias, int(stride), int(padding), 2 if relu_by_norm else int(bool(conv_relu)), stats, *xs)
+    # a strided convolution's data gradient is scatter-added into a zeroed dx: the norm's backward apply launch zero-fills it (_DxLink)
+    links = tuple(_DxLink() if c is not None and int(stride) > 1 and not _NO_DX_ZERO_BY_NORM else None for c in chains)
+    ys = _ConvFn.apply(weight, bias, int(stride), int(padding), 2 if relu_by_norm else int(bool(conv_relu)), stats, links, *xs)
     out = []
-    for y, bn, c in zip(ys, bns, chains):
+    for y, bn, c, link in zip(ys, bns, chains, links):
         if c is None:
             out.append(batch_norm(y, bn, relu=bn_relu))
         else:
             out.append(_BatchNormFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
-                                          True, int(bool(bn_relu)) | (2 if relu_by_norm else 0), c, True))
+                                          True, int(bool(bn_relu)) | (2 if relu_by_norm else 0), c, True, link))
     return out[0] if single else out
+
+
+class _DxLink(object):
+    """What the two autograd nodes of a conv -> BatchNorm block share (conv2d_batch_norm makes one per block): the norm's backward, which
+    runs first, allocates the convolution's dx and has its apply launch zero-fill it (ssdk_batchnorm_bwd_chained_ex); the convolution's
+    backward takes that tensor and tells the library that it is zero (ssdk_conv_desc::dx_is_zero) -- the zero-fill launch in front of a
+    scatter-form data gradient is gone.  Only when the library says the data gradient WILL take the scatter form (ssdk_conv2d_dx_form: the
+    plan's rule, with the deterministic flag of the moment), the input needs a gradient, and both nodes run in the same graph task on the
+    same stream; anything else -- and a tensor left over from a backward pass that raised -- is dropped and the call runs as without it."""
+    __slots__ = ('desc', 'shape', 'needs_dx', 'dx', 'task', 'stream')
+
+    def __init__(self):
+        self.desc = self.shape = self.dx = self.task = self.stream = None
+        self.needs_dx = False
+
+    def describe(self, x, cout, ksize, stride, pad, needs_dx):
+        d = self.desc = _lib.ConvDesc()
+        d.hin, d.win, d.cin, d.cout, d.ksize, d.stride, d.pad = x.shape[2], x.shape[3], x.shape[1], cout, ksize, stride, pad
+        self.shape, self.needs_dx = tuple(x.shape), bool(needs_dx)
+
+    def _scatter(self):
+        import ctypes
+        return self.desc is not None and _lib.lib().ssdk_conv2d_dx_form(ctypes.byref(self.desc)) == 1
+
+    def offer(self, device):
+        """(norm backward) the convolution's dx to zero-fill, or None."""
+        self.dx = None
+        if not self.needs_dx or not self._scatter():
+            return None
+        self.dx = torch.empty(self.shape, dtype=torch.float32, device=device, memory_format=torch.channels_last)
+        self.task, self.stream = torch._C._current_graph_task_id(), _lib.raw_stream(device)
+        return self.dx
+
+    def take(self, x):
+        """(convolution backward) the zero-filled dx of this graph task and stream, or None."""
+        dx, self.dx = self.dx, None
+        if dx is None or self.task != torch._C._current_graph_task_id() or self.stream != _lib.raw_stream(x.device):
+            return None
+        return dx if dx.shape == x.shape and dx.device == x.device and self._scatter() else None
 
 
 class _SumsChain(object):
@@ -608,7 +658,7 @@ class _SumsChain(object):
 
 class _BatchNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, training, relu, chain, sums_ready=False):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, training, relu, chain, sums_ready=False, link=None):
         lib = _lib.lib()
         _lib.require_cuda(x)
         x = _nhwc(x)
@@ -638,7 +688,7 @@ class _BatchNormFn(torch.autograd.Function):
                                               _lib.current_stream()), 'ssdk_batchnorm_fwd')
         ctx.save_for_backward(x, y if own else x.new_empty(0), g if g is not None else x.new_empty(0), mean, rstd)
         ctx.meta = (relu, bool(training), gamma is not None, beta is not None)
-        ctx.chain = chain
+        ctx.chain, ctx.link = chain, link
         ctx.mark_non_differentiable(mean, rstd)
         return y
 
@@ -654,16 +704,18 @@ class _BatchNormFn(torch.autograd.Function):
         dgamma = torch.empty((C,), dtype=torch.float32, device=x.device)
         dbeta = torch.empty((C,), dtype=torch.float32, device=x.device)
         if training and chain is not None and chain.usable(1, x.device):
-            _lib.check(lib.ssdk_batchnorm_bwd_chained(_dp(x), _dp(y) if relu & 1 else None, _dp(dy), B * H * W, C, _dp(g) if has_g else None, _dp(mean),
-                                                      _dp(rstd), relu, _dp(dx), _dp(dgamma), _dp(dbeta), chain.buf[1].data_ptr(),
-                                                      chain.buf[0].data_ptr(), _lib.current_stream()), 'ssdk_batchnorm_bwd_chained')
+            also = ctx.link.offer(x.device) if ctx.link is not None else None   # (the producing convolution's dx: zero-filled by the apply launch)
+            _lib.check(lib.ssdk_batchnorm_bwd_chained_ex(_dp(x), _dp(y) if relu & 1 else None, _dp(dy), B * H * W, C, _dp(g) if has_g else None, _dp(mean),
+                                                         _dp(rstd), relu, _dp(dx), _dp(dgamma), _dp(dbeta), chain.buf[1].data_ptr(),
+                                                         chain.buf[0].data_ptr(), _dp(also), 0 if also is None else also.numel(),
+                                                         _lib.current_stream()), 'ssdk_batchnorm_bwd_chained')
             chain.clean = [True, False]
         else:
             ws = _lib.scratch(lib.ssdk_batchnorm_workspace_bytes(C), x.device, 'batchnorm')
             _lib.check(lib.ssdk_batchnorm_bwd(_dp(x), _dp(y) if relu & 1 else None, _dp(dy), B * H * W, C, _dp(g) if has_g else None, _dp(mean),
                                               _dp(rstd), relu, int(training), _dp(dx), _dp(dgamma), _dp(dbeta), _dp(ws), ws.numel(),
                                               _lib.current_stream()), 'ssdk_batchnorm_bwd')
-        return dx, dgamma if has_g else None, dbeta if has_b else None, None, None, None, None, None, None, None, None, None
+        return dx, dgamma if has_g else None, dbeta if has_b else None, None, None, None, None, None, None, None, None, None, None
 
 
 def batch_norm(x, bn, relu=False):
