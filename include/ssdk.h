@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 122
+#define SSDK_VERSION 123
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -668,6 +668,24 @@ int ssdk_depthwise_conv2d_fwd(const float* x, const float* w, const float* bias,
                               int stride, int pad, float* y, void* stream);
 int ssdk_depthwise_conv2d_bwd(const float* x, const float* w, const float* dy, int batch, int hin, int win, int channels, int ksize,
                               int stride, int pad, float* dx, float* dw, float* db, int accumulate, void* stream);
+
+/* The forward of a depthwise Conv2dBn block -- depthwise k x k convolution -> BatchNorm2d -> ReLU (bf/modules/conv.py:30-36 with
+ * groups = channels), the `pyramid_output` blocks that FeaturePyramid(use_depthwise=True) builds (bf/modules/features.py:79-98: stride 1 /
+ * padding 1 on the tapped levels, stride 2 / padding 1 on the extra ones).  Arguments as ssdk_depthwise_conv2d_fwd's and checked by its
+ * rules (channels % 4 == 0, ksize <= 5, 16-byte aligned maps and bias); y and sums / the running statistics must not be NULL.  A refusal
+ * is SSDK_E_INVALID before any launch: nothing is written and ssdk_last_error_string() names the entry.  The backward is
+ * ssdk_depthwise_conv2d_bwd behind the norm's.
+ *   stats_fwd (training): y is ssdk_depthwise_conv2d_fwd's bit for bit, and the SAME launch adds the BatchNorm statistics of y to `sums`
+ *        [2 * channels + 2] doubles -- sum y into sums[0 .. C), sum y^2 into sums[C .. 2C), accumulated in fp64 from the first add -- and stores
+ *        sums[2C] = batch * hout * wout.  Like ssdk_batchnorm_stats_accumulate it ADDS to what is there (no zero-fill); the norm is then
+ *        ssdk_batchnorm_apply_chained alone.  One fp64 atomic per channel, sum and workgroup; at most ~256 workgroups add to one address.
+ *   norm_fwd (evaluation): ONE launch with the evaluation-mode norm (+ ReLU when relu != 0) in the stencil's epilogue; y is bit for bit
+ *        ssdk_depthwise_conv2d_fwd followed by ssdk_batchnorm_fwd(training = 0).  gamma / beta may be NULL (1 / 0); 16-byte aligned. */
+int ssdk_depthwise_conv2d_stats_fwd(const float* x, const float* w, const float* bias, int batch, int hin, int win, int channels, int ksize,
+                                    int stride, int pad, float* y, double* sums, void* stream);
+int ssdk_depthwise_conv2d_norm_fwd(const float* x, const float* w, const float* bias, int batch, int hin, int win, int channels, int ksize,
+                                   int stride, int pad, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, float eps, int relu, float* y, void* stream);
 
 /* The same stencil over 1 <= n_levels <= 8 maps that share batch, channels (% 4), weight [channels][k*k] and bias but have their own
  * hs[l] x ws[l]: the RetinaNet-lite tower of SharedConvPredictor(use_depthwise=True) (detection/modules/predictors.py:33-35,67-68), whose

@@ -39,16 +39,26 @@ class Conv2dBn(nn.Module):
             self.bn = nn.BatchNorm2d(out_channels, **batch_norm_params)
         if activation_params is not None:
             self.activation = getattr(nn, activation_params['name'])(**activation_params['args'])
-        # [cout][ky][kx][cin] memory = the rows the implicit GEMM reads (no per-step permute copy); state_dict unchanged
-        self.conv.weight.data = self.conv.weight.data.contiguous(memory_format=torch.channels_last)
+        # [cout][ky][kx][cin] memory = the rows the implicit GEMM reads (no per-step permute copy); state_dict unchanged.  A depthwise
+        # weight [C][1][k][k] is already what the stencil reads ([channels][k*k]) and is left as it is
+        if not self._is_depthwise():
+            self.conv.weight.data = self.conv.weight.data.contiguous(memory_format=torch.channels_last)
+
+    def _is_depthwise(self):
+        c = self.conv
+        return c.groups != 1 and c.groups == c.in_channels == c.out_channels
 
     def _why_not_hip(self):
         c = self.conv
         act = self._modules.get('activation')
-        if c.groups != 1:
+        dw = self._is_depthwise()
+        if c.groups != 1 and not dw:
+            if c.groups == c.in_channels:
+                return f'groups={c.groups} with a channel multiplier ({c.in_channels}->{c.out_channels} channels)'
             return f'groups={c.groups}'
-        if c.kernel_size not in ((1, 1), (3, 3)) or c.stride not in ((1, 1), (2, 2)) or c.dilation != (1, 1) or c.padding[0] != c.padding[1] \
-                or c.padding_mode != 'zeros':
+        # the implicit GEMM takes 1 x 1 and 3 x 3; the depthwise stencil (groups = channels in = channels out) any square kernel up to 5 x 5
+        kernel_ok = c.kernel_size[0] == c.kernel_size[1] and c.kernel_size[0] <= 5 if dw else c.kernel_size in ((1, 1), (3, 3))
+        if not kernel_ok or c.stride not in ((1, 1), (2, 2)) or c.dilation != (1, 1) or c.padding[0] != c.padding[1] or c.padding_mode != 'zeros':
             return f'kernel_size={c.kernel_size} stride={c.stride} dilation={c.dilation} padding={c.padding} ({c.padding_mode})'
         if c.in_channels % 4 or c.out_channels % 4:
             return f'channels {c.in_channels}->{c.out_channels} not multiples of 4'
@@ -60,9 +70,17 @@ class Conv2dBn(nn.Module):
         return self._why_not_hip() is None
 
     def forward(self, x):  # conv.py:30-36: conv -> BN -> activation
-        if self._hip_ok():   # libssdk: implicit-GEMM conv (csrc/conv.hip) + BatchNorm/ReLU kernels (csrc/norm.hip)
+        if self._hip_ok():
             has_bn, has_act = 'bn' in self._modules, 'activation' in self._modules
             c = self.conv
+            if self._is_depthwise():   # libssdk: depthwise stencil (csrc/norm.hip), the norm's statistics / the evaluation-mode norm in its launch
+                if has_bn and type(self.bn) is nn.BatchNorm2d:
+                    return ops.depthwise_conv2d_batch_norm(x, c.weight, c.bias, c.stride[0], c.padding[0], self.bn, relu=has_act)
+                x = ops.depthwise_conv2d_single(x, c.weight, c.bias, stride=c.stride[0], padding=c.padding[0])
+                if has_bn:
+                    return _norm_act(x, self.bn, self._modules.get('activation'))
+                return torch.relu(x) if has_act else x
+            # libssdk: implicit-GEMM conv (csrc/conv.hip) + BatchNorm/ReLU kernels (csrc/norm.hip)
             if has_bn and type(self.bn) is nn.BatchNorm2d:   # (statistics in the convolution's epilogue where they can be: ops.conv2d_batch_norm)
                 return ops.conv2d_batch_norm(x, c.weight, c.bias, c.stride[0], c.padding[0], self.bn, conv_relu=False, bn_relu=has_act)
             x = ops.conv2d(x, c.weight, c.bias, stride=c.stride[0], padding=c.padding[0], relu=has_act and not has_bn)
@@ -71,6 +89,10 @@ class Conv2dBn(nn.Module):
             return x
         # grouped / exotic variants (neck-side, out of the hot-path scope): stock PyTorch-ROCm modules
         _warn_stock('Conv2dBn', self._why_not_hip())
+        return self._forward_stock(x)
+
+    def _forward_stock(self, x):
+        """conv.py:30-36 on the stock PyTorch-ROCm modules."""
         x = self.conv(x)
         if 'bn' in self._modules:
             x = self.bn(x)

@@ -66,7 +66,10 @@ class Features(nn.Module):
 class FeaturePyramid(Features):
     """FPN neck -- restatement of bf/modules/features.py:52-120 (ref. arXiv:1612.03144), SURVEY.md §8f1.
 
-    Lateral 1x1 convs and the 3x3 output blocks run on libssdk's implicit-GEMM kernels (``ops.conv2d`` / ``Conv2dBn``), the
+    Lateral 1x1 convs and the 3x3 output blocks run on libssdk's implicit-GEMM kernels (``ops.conv2d`` / ``Conv2dBn``); with
+    ``use_depthwise`` (FPN-lite, features.py:79-98) every output block is ``Conv2dBn(C, C, 3, groups=C)`` -- stride 1 / padding 1 on the tapped
+    levels, stride 2 / padding 1 on the extra ones -- and runs on the depthwise stencil with the norm's statistics (training) or the whole
+    evaluation-mode norm in the stencil's launch (``ops.depthwise_conv2d_batch_norm``); the blocks pick that line by themselves.  The
     top-down ``features[i] += interpolate(features[i+1], interpolation_mode)`` on ``ssdk_upsample_nearest_add`` /
     ``ssdk_upsample_bilinear_add`` ('nearest' and 'bilinear' are on libssdk; any other mode is torch's interpolation, said once).  Module
     names (``pyramid_lateral``, ``pyramid_output``) follow the reference so checkpoints map 1:1."""
@@ -94,10 +97,15 @@ class FeaturePyramid(Features):
         self.pyramid_lateral.apply(self.init_layer)
         self.pyramid_output.apply(self.init_layer)
         for m in self.pyramid_output:   # init_layer rewrote the weights: restore the channels_last memory the GEMM reads
-            m.conv.weight.data = m.conv.weight.data.contiguous(memory_format=torch.channels_last)
+            if m.conv.groups == 1:      # (a depthwise weight [C][1][k][k] is what the stencil reads as it is)
+                m.conv.weight.data = m.conv.weight.data.contiguous(memory_format=torch.channels_last)
 
     def forward(self, x):
         sources, _ = super(FeaturePyramid, self).forward(x)
+        return self.neck(sources)
+
+    def neck(self, sources):
+        """Everything behind the backbone taps (features.py:105-117)."""
         if self.training:
             ops.prepare_weight_transposes(self.pyramid_lateral)
             ops.prepare_weight_transposes(self.pyramid_output)
@@ -214,7 +222,8 @@ class DepthwiseFeaturePyramid(Features):
         return output, output[-1]
 
     def _forward_stock(self, sources):
-        """features.py:180-209 as the reference runs it (stock modules; each block still picks its own path)."""
+        """features.py:180-209 as the reference runs it (stock modules; the downsample blocks still pick their own path, the depthwise
+        ``up_conv`` blocks run their stock line)."""
         features = [lateral(source) for source, lateral in zip(sources, self.pyramid_lateral)]
         for down in self.downsample:
             padding = [0, 0, 0, 0]
@@ -228,7 +237,7 @@ class DepthwiseFeaturePyramid(Features):
         output = [features[-1]]
         for i in reversed(range(0, len(features) - 1)):
             up = F.interpolate(output[-1], size=features[i].size()[2:], mode=self.interpolation_mode)
-            output.append(self.up_conv[i](up) + features[i])
+            output.append(self.up_conv[i]._forward_stock(up) + features[i])   # (the up step stays on the stock modules here)
         output = list(reversed(output))
         return output, output[-1]
 

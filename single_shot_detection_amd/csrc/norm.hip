@@ -203,6 +203,28 @@ __device__ __forceinline__ void stats_from_sums(const double* sums, double inv_n
 // 2 ulp off, which a beta that cancels most of gamma * xhat turns into several ulp of y)
 __device__ __forceinline__ float eval_rstd(float running_var, float eps) { return (float)rsqrt((double)running_var + (double)eps); }
 
+// The evaluation-mode constants of channel quad c, and the affine form of every forward apply: ((v - mean) * rstd) * gamma + beta, four
+// roundings.  Shared by bn_apply_kernel and the depthwise stencil's norm epilogue (dw_norm_fwd_kernel), which must give the same bits
+// as the stencil followed by the norm: each operation is an explicitly rounded one, so neither inlined copy can be contracted into a
+// multiply-add whatever flags the file is built with (bilinear_tap's argument).
+__device__ __forceinline__ void bn_eval_consts(const float* running_mean, const float* running_var, const float4* gamma, const float4* beta, float eps,
+                                               int c, float4& m, float4& rs, float4& ga, float4& be) {
+    m = reinterpret_cast<const float4*>(running_mean)[c];
+    const float4 rv = reinterpret_cast<const float4*>(running_var)[c];
+    rs = make_float4(eval_rstd(rv.x, eps), eval_rstd(rv.y, eps), eval_rstd(rv.z, eps), eval_rstd(rv.w, eps));
+    ga = gamma ? gamma[c] : make_float4(1.f, 1.f, 1.f, 1.f);
+    be = beta ? beta[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ float bn_affine(float v, float m, float rs, float ga, float be) {
+    return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(v, m), rs), ga), be);
+}
+__device__ __forceinline__ float4 bn_affine4(const float4 v, const float4 m, const float4 rs, const float4 ga, const float4 be, int relu) {
+    float4 o = make_float4(bn_affine(v.x, m.x, rs.x, ga.x, be.x), bn_affine(v.y, m.y, rs.y, ga.y, be.y), bn_affine(v.z, m.z, rs.z, ga.z, be.z),
+                           bn_affine(v.w, m.w, rs.w, ga.w, be.w));
+    if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+    return o;
+}
+
 __global__ void __launch_bounds__(256) bn_apply_kernel(const float4* __restrict__ x, long long n4, int C4, const float4* __restrict__ mean,
                                                        const float4* __restrict__ rstd, const float4* __restrict__ gamma,
                                                        const float4* __restrict__ beta, int relu, float4* __restrict__ y,
@@ -249,9 +271,8 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float4* __restrict_
             m = mean[c];
             rs = rstd[c];
         } else {   // evaluation mode: the running statistics (torch: 1 / sqrt(running_var + eps))
-            m = reinterpret_cast<const float4*>(running_mean)[c];
-            const float4 rv = reinterpret_cast<const float4*>(running_var)[c];
-            rs = make_float4(eval_rstd(rv.x, eps), eval_rstd(rv.y, eps), eval_rstd(rv.z, eps), eval_rstd(rv.w, eps));
+            bn_eval_consts(running_mean, running_var, gamma, beta, eps, c, m, rs, ga, be);
+            return;
         }
         ga = gamma ? gamma[c] : make_float4(1.f, 1.f, 1.f, 1.f);
         be = beta ? beta[c] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -260,11 +281,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float4* __restrict_
     if (fixed_c && i0 < n4) load_consts((int)(i0 % C4));
     for (long long i = i0; i < n4; i += stride) {
         if (!fixed_c) load_consts((int)(i % C4));
-        const float4 v = x[i];
-        float4 o = make_float4((v.x - m.x) * rs.x * ga.x + be.x, (v.y - m.y) * rs.y * ga.y + be.y, (v.z - m.z) * rs.z * ga.z + be.z,
-                               (v.w - m.w) * rs.w * ga.w + be.w);
-        if (relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-        y[i] = o;
+        y[i] = bn_affine4(x[i], m, rs, ga, be, relu);
     }
 }
 
@@ -1130,6 +1147,103 @@ __global__ void __launch_bounds__(256) dw_fwd_kernel(const float4* __restrict__ 
         y[i] = dw_fwd_point(x, w, bias, Hin, Win, C4, ks, taps, stride, pad, Hout, Wout, i);
 }
 
+// ---- the stencil of a depthwise Conv2dBn block (bf/modules/features.py:79-98: FeaturePyramid(use_depthwise=True) builds every
+// pyramid_output block as Conv2dBn(C, C, 3, groups=C); bf/modules/conv.py:30-36: conv -> BatchNorm -> ReLU) ----
+// Training: the stencil writes y and, in the same launch, adds the BatchNorm statistics of y to the layer's fp64 `sums` buffer -- the norm
+// behind it is one apply launch and the statistics pass over the activation is gone.  y is dw_fwd_point's, so the same bits as dw_fwd_kernel.
+//
+// The grid is (row blocks) x (column slabs), slabs innermost, as bn_reduce_kernel's: a workgroup owns `slab` channel quads (a power of two,
+// at most 16; the last slab of a C / 4 that slab does not divide is narrower, its spare lanes idle: C / 4 = 33) of rows_per_block output
+// pixels.  Thread t owns quad t % slab of the slab and the rows t / slab, t / slab + 256 / slab, ...: its channel quad never changes, whatever
+// C / 4 is, so its two fp64 accumulators are per-channel sums from the first add on (a flat grid-stride loop changes the quad from trip to
+// trip unless the stride is a multiple of C / 4).  fp64 for bn_reduce_kernel<0>'s reason: the variance is E[y^2] - mean^2 and the square
+// of an fp32 value is exact in fp64.  The lanes of a wave that share a quad are folded with cross-lane adds, the four waves through LDS,
+// all in fp64, and the workgroup ends with ONE fp64 atomic per channel and sum.
+//
+// Contention rule (dw_stats_plan): the workgroups that add to one address are the ROW blocks.  A stencil point is nine independent loads
+// and a store, far more work per row than a reduction's one load, and the launch needs many more workgroups than a reduction to cover the
+// memory latency: the rule aims at 256 row blocks (bn_reduce_plan: 64), each a whole number of trips of its slab (256 / slab rows), one trip
+// at the least -- a small map is all one-trip workgroups, as dw_fwd_kernel's one point per thread.  bn_rows_per_block's own measurement puts
+// the price of the same-address atomics at 15 - 20 ns per adder (1 984 -> 256 adders: 53 -> 23 us), so 256 adders are ~5 us spread over
+// the launch.  Measured (tools/bench_fpnlite.py, the neck at batch 32, forward + backward, SSDK_DW_STATS_WGS = 64 / 256 / 1024): 3.91 / 3.59 /
+// 3.60 ms at 256 channels, 3.04 / 2.81 / 2.81 ms at 128 (profiles/fpnlite_bench.txt).  SSDK_DW_STATS_WGS overrides the target.
+struct DwStatsPlan { int rows_per_block, slab, slabs; long long row_blocks; };
+static inline DwStatsPlan dw_stats_plan(long long rows, int C4) {
+    DwStatsPlan p;
+    p.slab = bn_pow2_at_least(C4 < 16 ? C4 : 16);
+    p.slabs = (C4 + p.slab - 1) / p.slab;
+    const char* e = getenv("SSDK_DW_STATS_WGS");
+    long long target = e ? atoll(e) : 256;
+    if (target < 1) target = 1;
+    const int rpt = 256 / p.slab;   // rows per trip of a workgroup
+    long long r = (rows + target - 1) / target;
+    r = (r + rpt - 1) / rpt * rpt;
+    if (r < rpt) r = rpt;
+    p.rows_per_block = (int)(r > (1 << 20) ? (1 << 20) : r);
+    p.row_blocks = (rows + p.rows_per_block - 1) / p.rows_per_block;
+    return p;
+}
+
+__global__ void __launch_bounds__(256) dw_stats_fwd_kernel(const float4* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, int B,
+                                                           int Hin, int Win, int C4, int ks, int stride, int pad, int Hout, int Wout, int rows_per_block,
+                                                           int slab, int slabs, float4* __restrict__ y, double* __restrict__ sums) {
+    __shared__ bn_acc4<double> s_part[2 * 4 * 64];   // [sum][wave][lane]
+    const long long rows = (long long)B * Hout * Wout;
+    const int C = C4 * 4, taps = ks * ks;
+    const int my_slab = (int)(blockIdx.x % (unsigned)slabs);
+    const long long r0 = (long long)(blockIdx.x / (unsigned)slabs) * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = threadIdx.x & (slab - 1), sub = threadIdx.x / slab, rpt = 256 / slab;
+    const int c4 = my_slab * slab + col;
+    if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = (double)rows;   // (slot 2C: the count behind the sums)
+    bn_acc4<double> a0 = {0, 0, 0, 0}, a1 = a0;
+    if (c4 < C4) {
+        for (long long r = r0 + sub; r < r1; r += rpt) {
+            const long long i = r * C4 + c4;
+            const float4 v = dw_fwd_point(x, w, bias, Hin, Win, C4, ks, taps, stride, pad, Hout, Wout, i);
+            y[i] = v;
+            const double v0 = v.x, v1 = v.y, v2 = v.z, v3 = v.w;
+            a0.x += v0; a0.y += v1; a0.z += v2; a0.w += v3;
+            a1.x += v0 * v0; a1.y += v1 * v1; a1.z += v2 * v2; a1.w += v3 * v3;
+        }
+    }
+    // lanes col, col + slab, ... of a wave hold the same quad (slab divides 64): fold them into lane col, then the four waves through LDS
+    for (int d = slab; d < 64; d <<= 1) {
+        a0.x += __shfl_xor(a0.x, d, 64); a0.y += __shfl_xor(a0.y, d, 64); a0.z += __shfl_xor(a0.z, d, 64); a0.w += __shfl_xor(a0.w, d, 64);
+        a1.x += __shfl_xor(a1.x, d, 64); a1.y += __shfl_xor(a1.y, d, 64); a1.z += __shfl_xor(a1.z, d, 64); a1.w += __shfl_xor(a1.w, d, 64);
+    }
+    s_part[(0 * 4 + wave) * 64 + lane] = a0;
+    s_part[(1 * 4 + wave) * 64 + lane] = a1;
+    __syncthreads();
+    if (wave < 2 && lane < slab && my_slab * slab + lane < C4) {   // wave 0 folds the sums, wave 1 the sums of squares (lane < slab: col == lane)
+        bn_acc4<double> t = s_part[(wave * 4 + 0) * 64 + lane];
+        for (int k = 1; k < 4; ++k) { const bn_acc4<double> u = s_part[(wave * 4 + k) * 64 + lane]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+        double* dst = sums + (size_t)wave * C + (size_t)(my_slab * slab + lane) * 4;
+        atomicAdd(dst + 0, t.x); atomicAdd(dst + 1, t.y); atomicAdd(dst + 2, t.z); atomicAdd(dst + 3, t.w);
+    }
+}
+
+// Inference: the stencil with the evaluation-mode BatchNorm (+ ReLU) in its epilogue -- one launch instead of three, the same bits as
+// dw_fwd_kernel followed by bn_apply_kernel's evaluation branch (dw_fwd_point, bn_eval_consts and bn_affine4 are shared with them).  The grid
+// is apply_blocks': a thread keeps its channel quad over its trips and derives the four reciprocal square roots once.
+__global__ void __launch_bounds__(256) dw_norm_fwd_kernel(const float4* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, int B,
+                                                          int Hin, int Win, int C4, int ks, int stride, int pad, int Hout, int Wout,
+                                                          const float4* __restrict__ gamma, const float4* __restrict__ beta,
+                                                          const float* __restrict__ running_mean, const float* __restrict__ running_var, float eps,
+                                                          int relu, float4* __restrict__ y) {
+    const long long total = (long long)B * Hout * Wout * C4;
+    const int taps = ks * ks;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    const bool fixed_c = step % C4 == 0;
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f), rs = m, ga = m, be = m;
+    const long long i0 = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (fixed_c && i0 < total) bn_eval_consts(running_mean, running_var, gamma, beta, eps, (int)(i0 % C4), m, rs, ga, be);
+    for (long long i = i0; i < total; i += step) {
+        if (!fixed_c) bn_eval_consts(running_mean, running_var, gamma, beta, eps, (int)(i % C4), m, rs, ga, be);
+        y[i] = bn_affine4(dw_fwd_point(x, w, bias, Hin, Win, C4, ks, taps, stride, pad, Hout, Wout, i), m, rs, ga, be, relu);
+    }
+}
+
 // dx[b,iy,ix,c] = sum over taps with (iy + pad - ky) % stride == 0 ... of w[c][tap] * dy[b,(iy+pad-ky)/stride,(ix+pad-kx)/stride,c]
 // (one input element, added to `acc`: shared by the single-level and the grouped kernels)
 __device__ __forceinline__ float4 dw_dgrad_point(const float4* dy, const float* w, int Hin, int Win, int C4, int ks, int taps,
@@ -1360,6 +1474,44 @@ extern "C" int ssdk_depthwise_conv2d_fwd(const float* x, const float* w, const f
     hipLaunchKernelGGL(ssdk::dw_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(x), w, bias, batch, hin, win,
                        channels / 4, ksize, stride, pad, ho, wo, reinterpret_cast<float4*>(y));
     SSDK_CHECK_LAUNCH("dw_fwd_kernel");
+    return SSDK_OK;
+}
+
+// the forward of a training-mode depthwise Conv2dBn block: y as ssdk_depthwise_conv2d_fwd's, and sums += the statistics of y (no zero-fill:
+// ssdk_batchnorm_stats_accumulate's contract), sums[2C] = the row count
+extern "C" int ssdk_depthwise_conv2d_stats_fwd(const float* x, const float* w, const float* bias, int batch, int hin, int win, int channels, int ksize,
+                                               int stride, int pad, float* y, double* sums, void* stream) {
+    const char* fn = "ssdk_depthwise_conv2d_stats_fwd";
+    int rc = dw_check(fn, batch, hin, win, channels, ksize, stride, pad);
+    if (rc) return rc;
+    SSDK_REQUIRE(x && w && y && sums && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)sums & 7) == 0, SSDK_E_INVALID,
+                 "%s: null or unaligned pointer (y and sums are required)", fn);
+    const int ho = (hin + 2 * pad - ksize) / stride + 1, wo = (win + 2 * pad - ksize) / stride + 1, c4 = channels / 4;
+    const long long rows = (long long)batch * ho * wo;
+    const ssdk::DwStatsPlan p = ssdk::dw_stats_plan(rows, c4);
+    SSDK_REQUIRE(p.row_blocks * p.slabs < (1ll << 31), SSDK_E_INVALID, "%s: %lld row blocks x %d slabs exceed the grid", fn, p.row_blocks, p.slabs);
+    hipLaunchKernelGGL(ssdk::dw_stats_fwd_kernel, dim3((unsigned)(p.row_blocks * p.slabs)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(x),
+                       w, bias, batch, hin, win, c4, ksize, stride, pad, ho, wo, p.rows_per_block, p.slab, p.slabs, reinterpret_cast<float4*>(y), sums);
+    SSDK_CHECK_LAUNCH("dw_stats_fwd_kernel");
+    return SSDK_OK;
+}
+
+// the forward of an evaluation-mode depthwise Conv2dBn block in one launch: ssdk_depthwise_conv2d_fwd, then ssdk_batchnorm_fwd(training = 0)
+extern "C" int ssdk_depthwise_conv2d_norm_fwd(const float* x, const float* w, const float* bias, int batch, int hin, int win, int channels, int ksize,
+                                              int stride, int pad, const float* gamma, const float* beta, const float* running_mean,
+                                              const float* running_var, float eps, int relu, float* y, void* stream) {
+    const char* fn = "ssdk_depthwise_conv2d_norm_fwd";
+    int rc = dw_check(fn, batch, hin, win, channels, ksize, stride, pad);
+    if (rc) return rc;
+    SSDK_REQUIRE(x && w && y && running_mean && running_var, SSDK_E_INVALID, "%s: null pointer (y and the running statistics are required)", fn);
+    SSDK_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)running_mean | (uintptr_t)running_var) & 15) == 0,
+                 SSDK_E_INVALID, "%s: unaligned pointer (16 bytes: maps, bias, gamma, beta, running statistics)", fn);
+    const int ho = (hin + 2 * pad - ksize) / stride + 1, wo = (win + 2 * pad - ksize) / stride + 1, c4 = channels / 4;
+    const long long total = (long long)batch * ho * wo * c4;
+    hipLaunchKernelGGL(ssdk::dw_norm_fwd_kernel, dim3(ssdk::apply_blocks(total, c4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(x), w, bias,
+                       batch, hin, win, c4, ksize, stride, pad, ho, wo, reinterpret_cast<const float4*>(gamma), reinterpret_cast<const float4*>(beta),
+                       running_mean, running_var, eps, relu, reinterpret_cast<float4*>(y));
+    SSDK_CHECK_LAUNCH("dw_norm_fwd_kernel");
     return SSDK_OK;
 }
 

@@ -1123,7 +1123,9 @@ class _DepthwiseFn(torch.autograd.Function):
     """Depthwise k x k convolution (groups = channels) on libssdk; weight is torch's [C, 1, k, k] parameter."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad):
+    def forward(ctx, x, weight, bias, stride, pad, stats=None):
+        """stats: None, or the address of an fp64 `sums` buffer: the same launch adds the BatchNorm statistics of y to it
+        (ssdk_depthwise_conv2d_stats_fwd; depthwise_conv2d_batch_norm)."""
         lib = _lib.lib()
         _lib.require_cuda(x, weight)
         x = _nhwc(x)
@@ -1133,8 +1135,12 @@ class _DepthwiseFn(torch.autograd.Function):
         b = None if bias is None else bias.float().contiguous()
         ho, wo = _out_dim(H, k, stride, pad), _out_dim(W, k, stride, pad)
         y = torch.empty((B, C, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        _lib.check(lib.ssdk_depthwise_conv2d_fwd(_dp(x), _dp(w), _dp(b), B, H, W, C, k, stride, pad, _dp(y), _lib.current_stream()),
-                   'ssdk_depthwise_conv2d_fwd')
+        if stats is None:
+            _lib.check(lib.ssdk_depthwise_conv2d_fwd(_dp(x), _dp(w), _dp(b), B, H, W, C, k, stride, pad, _dp(y), _lib.current_stream()),
+                       'ssdk_depthwise_conv2d_fwd')
+        else:
+            _lib.check(lib.ssdk_depthwise_conv2d_stats_fwd(_dp(x), _dp(w), _dp(b), B, H, W, C, k, stride, pad, _dp(y), stats, _lib.current_stream()),
+                       'ssdk_depthwise_conv2d_stats_fwd')
         ctx.save_for_backward(x, w)
         ctx.meta = (stride, pad, bias is not None)
         return y
@@ -1152,7 +1158,7 @@ class _DepthwiseFn(torch.autograd.Function):
         db = torch.empty((C,), dtype=torch.float32, device=x.device) if has_bias else None
         _lib.check(lib.ssdk_depthwise_conv2d_bwd(_dp(x), _dp(w), _dp(dy), B, H, W, C, k, stride, pad, _dp(dx), _dp(dw), _dp(db), 0,
                                                  _lib.current_stream()), 'ssdk_depthwise_conv2d_bwd')
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
 class _DepthwiseGroupFn(torch.autograd.Function):
@@ -1226,6 +1232,67 @@ def depthwise_conv2d(x, weight, bias=None, stride=1, padding=0):
     if isinstance(x, torch.Tensor):
         return _DepthwiseFn.apply(x, weight, bias, int(stride), int(padding))
     return list(_DepthwiseGroupFn.apply(weight, bias, int(stride), int(padding), *x))
+
+
+def depthwise_conv2d_batch_norm(x, weight, bias, stride, padding, bn, relu=False):
+    """depthwise conv -> BatchNorm (-> ReLU) of one map: a Conv2dBn block with groups = channels (bf/modules/conv.py:30-36; the
+    `pyramid_output` blocks of FeaturePyramid(use_depthwise=True), bf/modules/features.py:79-98).
+      training, a plain BatchNorm2d with per-process statistics and a clean `sums` chain: the stencil's launch accumulates the norm's
+        statistics (ssdk_depthwise_conv2d_stats_fwd) and the norm is ONE apply launch -- no statistics pass over the activation
+        (SSDK_NO_FUSED_STATS: off, the two-pass form);
+      evaluation, a plain BatchNorm2d, nothing needs a gradient: ONE launch (ssdk_depthwise_conv2d_norm_fwd), the same bits as the two
+        (which SSDK_NO_FUSED_STATS brings back as well);
+      anything else (a norm marked for synchronisation, evaluation with gradients, a chain that is not clean, momentum=None, deterministic
+        mode, an output above _DW_STATS_MAX_N4 where the two-pass form measured faster): depthwise_conv2d followed by batch_norm."""
+    stride, padding = int(stride), int(padding)
+    plain = type(bn) is torch.nn.BatchNorm2d and x.is_cuda and weight.shape[0] % 4 == 0
+    chain = _local_training_chain(bn, x.device) if plain and torch.is_grad_enabled() and _dw_stats_fused(x, weight, stride, padding) else None
+    if chain is not None:
+        global fused_stats_calls
+        chain.clean[0] = False   # (handed to the stencil: whatever happens next, it no longer holds zeros)
+        fused_stats_calls += 1
+        y = _DepthwiseFn.apply(x, weight, bias, stride, padding, chain.buf[0].data_ptr())
+        return _BatchNormFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                                  True, int(bool(relu)), chain, True, None)
+    if (plain and not _NO_FUSED_STATS and not bn.training and bn.momentum is not None and bn.track_running_stats
+            and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, bn.weight, bn.bias)))):
+        lib = _lib.lib()
+        _lib.require_cuda(x, weight)
+        x = _nhwc(x)
+        B, C, H, W = x.shape
+        k = weight.shape[-1]
+        w = weight.detach().float().contiguous()
+        b, g, be = [None if t is None else t.detach().float().contiguous() for t in (bias, bn.weight, bn.bias)]
+        y = torch.empty((B, C, _out_dim(H, k, stride, padding), _out_dim(W, k, stride, padding)), dtype=torch.float32, device=x.device,
+                        memory_format=torch.channels_last)
+        _lib.check(lib.ssdk_depthwise_conv2d_norm_fwd(_dp(x), _dp(w), _dp(b), B, H, W, C, k, stride, padding, _dp(g), _dp(be), _dp(bn.running_mean),
+                                                      _dp(bn.running_var), float(bn.eps), int(bool(relu)), _dp(y), _lib.current_stream()),
+                   'ssdk_depthwise_conv2d_norm_fwd')
+        return y
+    return batch_norm(depthwise_conv2d_single(x, weight, bias, stride, padding), bn, relu=relu)
+
+
+# Above this many float4 elements of output the statistics stay a pass of their own: on the 63 x 63 x 256 map at batch 32 (8.1 M float4) the
+# stencil + bn_reduce pair takes 304 us and the fused launch 325; at 32 x 32 (2.1 M) they tie at 95 us, below it the fused launch wins
+# (16 x 16: 32 against 36 us) -- profiles/fpnlite_kernel_stats.md.  SSDK_DW_STATS_MAX_N4 overrides (measurement knob).
+_DW_STATS_MAX_N4 = int(__import__('os').environ.get('SSDK_DW_STATS_MAX_N4') or (1 << 21))
+
+
+def _dw_stats_fused(x, weight, stride, padding):
+    k = weight.shape[-1]
+    n4 = x.shape[0] * _out_dim(x.shape[2], k, stride, padding) * _out_dim(x.shape[3], k, stride, padding) * (x.shape[1] // 4)
+    # deterministic mode: the block's backward is the grouped entry's (depthwise_conv2d_single), and its forward the plain two-pass form
+    return n4 <= _DW_STATS_MAX_N4 and not is_deterministic()
+
+
+def depthwise_conv2d_single(x, weight, bias=None, stride=1, padding=0):
+    """depthwise_conv2d of one map for a block whose maps can be large (the FPN-lite neck).  In deterministic mode the weight gradient of
+    ssdk_depthwise_conv2d_bwd is ONE workgroup per 64 channel quads walking every pixel -- fine on the few-pixel maps of the SSD extras, 40 x
+    the stock modules' time on a 63 x 63 map at batch 32 -- so there the map goes through the grouped entry as a group of one: its two-launch
+    weight gradient has no atomics and the same bits in both modes."""
+    if is_deterministic():
+        return _DepthwiseGroupFn.apply(weight, bias, int(stride), int(padding), x)[0]
+    return _DepthwiseFn.apply(x, weight, bias, int(stride), int(padding))
 
 
 # ---- depthwise feature pyramid (Tiny-DSOD D-FPN, bf/modules/features.py:123-212) ------------------------------------------------
