@@ -2,7 +2,16 @@
 
 Tensors are logical [B,C,H,W] with channels_last memory (= the NHWC buffers the kernels read); weights are logical
 [Cout,Cin,k,k] with channels_last memory (= [Cout][k][k][Cin]).  GPU only -- CPU tensors raise.
+
+The convolution half does each job once: ``_set_desc`` is the only writer of a ``ssdk_conv_desc``, ``_conv_out`` allocates a forward
+output, ``_upstream_grad`` prepares what autograd delivers, ``_grad_targets`` says where a parameter's gradient goes, ``_may_defer`` whether
+it may wait for the end of the pass, and ``_conv_backward`` is the backward of both convolution Functions (and ``_flush_jobs`` that of the
+deferred weight gradients).  ``_sums_chain_of`` / ``_norm_of_ready_sums`` wire a BatchNorm to the convolution that took its statistics.
 """
+import ctypes
+import os
+import weakref
+
 import torch
 
 from . import _lib
@@ -21,9 +30,58 @@ def _out_dim(n, k, s, p):
     return (n + 2 * p - k) // s + 1
 
 
+def _conv_out(x, cout, k, stride, pad):
+    """The (uninitialised) output map of a k x k convolution of the NHWC map ``x`` to ``cout`` channels."""
+    batch, _, hin, win = x.shape
+    return torch.empty((batch, cout, _out_dim(hin, k, stride, pad), _out_dim(win, k, stride, pad)), dtype=torch.float32, device=x.device,
+                       memory_format=torch.channels_last)
+
+
+def _set_desc(d, hin, win, cin, cout, ksize, stride, pad, x=None, w=None, bias=None, relu=0, y=None, stats=None,
+              dy=None, dx=None, dw=None, db=None, w_t=None, dx_is_zero=False):
+    """Writes the ssdk_conv_desc ``d`` -- the ONLY place in this module that assigns a field of one, so a field added to the ABI is threaded
+    through here and nowhere else.  The geometry is explicit (SFAM's [n_scales, B, C] rows are 1 x 1 maps; prepare_weight_transposes and
+    _DxLink.describe give nothing but geometry); the operands are tensors (None or empty: a null pointer), ``stats`` is the address of an
+    fp64 `sums` buffer.  ``d`` is fresh (ctypes made it all zeros) and each call writes the half it is for: without ``dy`` the forward
+    operands, with it the backward ones (a backward entry point reads neither bias nor y)."""
+    d.hin, d.win, d.cin, d.cout, d.ksize, d.stride, d.pad, d.relu = hin, win, cin, cout, ksize, stride, pad, relu
+    d.x, d.w = _dp(x), _dp(w)
+    if dy is None:
+        d.bias, d.y, d.stats = _dp(bias), _dp(y), stats
+    else:
+        d.dy, d.dx, d.dw, d.db, d.w_t, d.dx_is_zero = _dp(dy), _dp(dx), _dp(dw), _dp(db), _dp(w_t), int(dx_is_zero)
+
+
+def _upstream_grad(dy, shape, device, y=None, stream=None):
+    """What autograd delivered for an output of ``shape``, as the NHWC fp32 map the library reads: zeros for an output nobody used
+    downstream (None), and -- ``y``: the saved output of a forward that fused a ReLU -- with that ReLU undone (ssdk_relu_bwd)."""
+    dy = torch.zeros(shape, dtype=torch.float32, device=device).contiguous(memory_format=torch.channels_last) if dy is None else _nhwc(dy)
+    if y is None:
+        return dy
+    g = torch.empty_like(dy, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().ssdk_relu_bwd(_dp(y), _dp(dy), dy.numel(), _dp(g), stream), 'ssdk_relu_bwd')
+    return g
+
+
+def _grad_targets(w, weight, bias, need_w, need_b):
+    """(dw, db): where the library writes (it zeroes them first) the gradients of the parameters ``weight`` -- saved as ``w`` -- and
+    ``bias``; None where not needed.  A parameter's slot in a gradient bucket (distributed.GradBucket) when it has one -- for a weight, one
+    laid out like ``w`` -- and a fresh tensor otherwise."""
+    dw = db = None
+    if need_w:
+        dw = grad_sink(weight)
+        if dw is None or dw.stride() != w.stride():
+            dw = torch.empty_like(w, memory_format=torch.channels_last)
+    if need_b:
+        db = grad_sink(bias)
+        if db is None:
+            db = torch.empty((w.shape[0],), dtype=torch.float32, device=w.device)
+    return dw, db
+
+
 def _fast_min_flops():
     """fast mode: smaller launches stay fp32 (the library applies the same bound, from the same variable, to the data gradients)."""
-    e = __import__('os').environ.get('SSDK_FAST_MIN_FLOPS')
+    e = os.environ.get('SSDK_FAST_MIN_FLOPS')
     return float(e) if e else 1.0e9
 
 
@@ -46,17 +104,12 @@ class _ConvFn(torch.autograd.Function):
         arr = (_lib.ConvDesc * len(xs))()
         for i, x in enumerate(xs):
             assert x.shape[0] == B and x.shape[1] == cin, (tuple(x.shape), cin)
-            ho, wo = _out_dim(x.shape[2], k, stride, pad), _out_dim(x.shape[3], k, stride, pad)
-            y = torch.empty((B, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            y = _conv_out(x, cout, k, stride, pad)
             ys.append(y)
-            d = arr[i]
-            d.x, d.hin, d.win, d.cin = _dp(x), x.shape[2], x.shape[3], cin
-            d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = _dp(w), _dp(b), cout, k, stride, pad, int(bool(relu))
-            d.y = _dp(y)
-            d.stats = None if stats is None else stats[i]
+            _set_desc(arr[i], x.shape[2], x.shape[3], cin, cout, k, stride, pad, x, w, b, int(bool(relu)), y, None if stats is None else stats[i])
         # opt-in split-bf16 forward (heads.set_fast_mode) -- for launches of at least ~1 GFLOP: below that the split of the weights and the
         # statistics pass behind the launch cost more than three bf16 MFMAs save over one fp32 one (the SSD tail's small layers)
-        flops = 2.0 * B * cout * cin * k * k * sum(_out_dim(x.shape[2], k, stride, pad) * _out_dim(x.shape[3], k, stride, pad) for x in xs)
+        flops = 2.0 * B * cout * cin * k * k * sum(y.shape[2] * y.shape[3] for y in ys)
         if _lib.fast_mode == 'bf16x3' and cin % 32 == 0 and flops >= _fast_min_flops():
             fw = _lib.scratch(lib.ssdk_conv2d_fwd_fast_workspace_bytes(arr, len(xs)), xs[0].device, 'conv_fwd_fast')
             _lib.check(lib.ssdk_conv2d_fwd_fast(arr, len(xs), B, 3, _dp(fw), fw.numel(), _lib.current_stream()), 'ssdk_conv2d_fwd_fast')
@@ -76,65 +129,73 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dys):
-        lib = _lib.lib()
         stride, pad, relu, n, has_bias, yshapes = ctx.meta
         saved = ctx.saved_tensors
         w, xs = saved[0], saved[1:1 + n]
-        ys = saved[1 + n:] if relu else [None] * n
-        cout, cin, k, _ = w.shape
-        B = xs[0].shape[0]
-        stream = _lib.current_stream()
-        need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and has_bias
+        ys = saved[1 + n:] if relu else [None] * n   # (relu: undo the ReLU fused into the forward epilogue)
+        weight, bias = ctx.params
+        need = ctx.needs_input_grad
+        need_w, need_b = need[0], need[1] and has_bias
         # weight gradients of single-input convolutions can wait for the end of the backward pass: nothing in the chain depends on
         # them, and eight small launches that each underfill the chip become one grouped launch (_flush_weight_gradients)
-        defer = (_defer_wgrad and n == 1 and (need_w or need_b) and ctx.params[0].is_leaf and (ctx.params[1] is None or ctx.params[1].is_leaf)
-                 and not _has_hooks(ctx.params[0]) and not _has_hooks(ctx.params[1]))
-        dw = db = None
-        if need_w and not defer:   # zeroed by the library
-            dw = grad_sink(ctx.params[0])
-            if dw is None or dw.stride() != w.stride():
-                dw = torch.empty_like(w, memory_format=torch.channels_last)
-        if need_b and not defer:
-            db = grad_sink(ctx.params[1])
-            if db is None:
-                db = torch.empty((cout,), dtype=torch.float32, device=w.device)
-        arr = (_lib.ConvDesc * n)()
-        dxs, keep = [], []
-        for i in range(n):
-            x = xs[i]
-            dy = dys[i]   # an output nobody used downstream arrives as None
-            dy = torch.zeros(yshapes[i], dtype=torch.float32, device=w.device).contiguous(memory_format=torch.channels_last) if dy is None else _nhwc(dy)
-            if relu:  # undo the ReLU fused into the forward epilogue
-                g = torch.empty_like(dy, memory_format=torch.channels_last)
-                _lib.check(lib.ssdk_relu_bwd(_dp(ys[i]), _dp(dy), dy.numel(), _dp(g), stream), 'ssdk_relu_bwd')
-                dy = g
-            keep.append(dy)
-            # (a dx that the consumer norm's backward apply launch has zero-filled in this graph task, on this stream: _DxLink)
-            zeroed = ctx.links[i].take(x) if ctx.links and ctx.links[i] is not None and ctx.needs_input_grad[7 + i] else None
-            dx = zeroed if zeroed is not None else (torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[7 + i] else None)
-            dxs.append(dx)
-            d = arr[i]
-            d.x, d.hin, d.win, d.cin = _dp(x), x.shape[2], x.shape[3], cin
-            d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = _dp(w), None, cout, k, stride, pad, 0
-            d.dy, d.dx, d.dw, d.db = _dp(dy), _dp(dx), _dp(dw), _dp(db)
-            d.w_t = _dp(ctx.w_t)
-            d.dx_is_zero = int(zeroed is not None)
+        defer = n == 1 and (need_w or need_b) and _may_defer(weight, bias)
+        links = ctx.links or [None] * n
+        grads, launched = _conv_backward([(w, weight, bias, need_w, need_b, defer, xs[i], ys[i], dys[i], yshapes[i], stride, pad, need[7 + i],
+                                           ctx.w_t, links[i]) for i in range(n)], shared=True)
+        if launched:   # (a deferred call whose inputs need no gradient has nothing to compute: every gradient below is None)
+            _forget_transposed_weights(weight)
+        return (grads[1], grads[2], None, None, None, None, None) + tuple(grads[0::3])
+
+
+def _may_defer(weight, bias):
+    """May the gradients of this weight / bias pair wait for the end of the backward pass (defer_weight_gradients)?  Leaf parameters
+    without hooks only: the flush writes ``.grad`` itself."""
+    return _defer_wgrad and weight.is_leaf and (bias is None or bias.is_leaf) and not _has_hooks(weight) and not _has_hooks(bias)
+
+
+def _conv_backward(probs, shared):
+    """The backward pass of one grouped convolution call: allocates, describes, queues the deferred jobs, launches (unless nothing is to
+    be computed).  ``probs``: one tuple per problem,
+        (w, weight, bias, need_w, need_b, defer, x, y, dy, yshape, stride, pad, need_x, w_t, link)
+    w, x: the saved weight and input;  weight, bias: the parameters (their gradient-bucket slots, the deferred jobs);  need_*: which
+    gradients are wanted;  defer: dw / db wait for _flush_weight_gradients;  y: the saved output where the forward fused a ReLU, else
+    None;  dy: what autograd delivered, of shape yshape;  w_t: the prepared transposed weight, or None;  link: a _DxLink, or None.
+    ``shared``: the problems share ONE weight and bias (_ConvFn) and the library accumulates one dw / db over the list; otherwise
+    (_GroupConvFn) every problem has its own.  Returns ([dx, dw, db of problem 0, dx, dw, db of problem 1, ...], launched)."""
+    lib = _lib.lib()
+    stream = _lib.current_stream()
+    n = len(probs)
+    if shared:
+        w, weight, bias, need_w, need_b, defer = probs[0][:6]
+        dw, db = _grad_targets(w, weight, bias, need_w and not defer, need_b and not defer)
+    arr = (_lib.ConvDesc * n)()
+    grads, keep = [], []   # keep: every prepared dy lives until the launch is enqueued (its block must not be handed to a later dx)
+    launch = False
+    for i, (w, weight, bias, need_w, need_b, defer, x, y, dy, yshape, stride, pad, need_x, w_t, link) in enumerate(probs):
+        dy = _upstream_grad(dy, yshape, w.device, y, stream)
+        keep.append(dy)
+        if not shared:
+            dw, db = _grad_targets(w, weight, bias, need_w and not defer, need_b and not defer)
+        # (a dx that the consumer norm's backward apply launch has zero-filled in this graph task, on this stream: _DxLink)
+        zeroed = link.take(x) if link is not None and need_x else None
+        dx = zeroed if zeroed is not None else (torch.empty_like(x, memory_format=torch.channels_last) if need_x else None)
+        cout, cin, k, _ = w.shape
+        _set_desc(arr[i], x.shape[2], x.shape[3], cin, cout, k, stride, pad, x, w, dy=dy, dx=dx, dw=dw, db=db, w_t=w_t, dx_is_zero=zeroed is not None)
         if defer:
             # jobs belong to ONE autograd graph task: a backward pass that raised leaves its callbacks unrun and its jobs behind -- they are
             # dropped (never added into a later step's gradients), and the flush is queued once per task, not "when the list was empty"
-            _queue_deferred_wgrad(dict(x=xs[0], dy=keep[0], w=w, weight=ctx.params[0] if need_w else None, bias=ctx.params[1] if need_b else None,
-                                       stride=stride, pad=pad))
-            if all(dx is None for dx in dxs):
-                return (None, None, None, None, None, None, None) + tuple(dxs)
-        _conv2d_bwd(lib, arr, n, B, w.device, stream)
-        _forget_transposed_weights(ctx.params[0])
-        return (dw, db, None, None, None, None, None) + tuple(dxs)
+            _queue_deferred_wgrad(dict(x=x, dy=dy, w=w, weight=weight if need_w else None, bias=bias if need_b else None, stride=stride, pad=pad))
+        launch = launch or dx is not None or dw is not None or db is not None
+        grads += (dx, dw, db)
+    if launch:
+        _conv2d_bwd(lib, arr, n, probs[0][6].shape[0], probs[0][0].device, stream)
+    return grads, launch
 
 
 # stream-K for the generic convolutions: the library takes it for launches of two rounds of tiles and more (conv.hip streamk_would_take:
 # the RetinaNet tower, the large maps of the M2Det neck; slower on the one-round launches of a pyramid tail), so these calls carry the
 # heads' 33 MB stream-K workspace (one cached buffer per device and stream); SSDK_CONV_STREAMK_GENERIC=0: never, no workspace.  Read once
-_GENERIC_STREAMK = __import__('os').environ.get('SSDK_CONV_STREAMK_GENERIC', '') != '0'
+_GENERIC_STREAMK = os.environ.get('SSDK_CONV_STREAMK_GENERIC', '') != '0'
 
 
 def _conv2d_fwd(lib, arr, n, batch, device):
@@ -184,14 +245,9 @@ class _GroupConvFn(torch.autograd.Function):
             x, w = xs[i], ws[i]
             cout, cin, k, k2 = w.shape
             assert k == k2 and x.shape[0] == B and x.shape[1] == cin, (tuple(x.shape), tuple(w.shape))
-            ho, wo = _out_dim(x.shape[2], k, stride, pad), _out_dim(x.shape[3], k, stride, pad)
-            y = torch.empty((B, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            y = _conv_out(x, cout, k, stride, pad)
             ys.append(y)
-            d = arr[i]
-            d.x, d.hin, d.win, d.cin = _dp(x), x.shape[2], x.shape[3], cin
-            d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = _dp(w), _dp(bs[i]), cout, k, stride, pad, int(bool(relu))
-            d.y = _dp(y)
-            d.stats = stats
+            _set_desc(arr[i], x.shape[2], x.shape[3], cin, cout, k, stride, pad, x, w, bs[i], int(bool(relu)), y, stats)
         _conv2d_fwd(lib, arr, n, B, xs[0].device)
         ctx.w_ts = [_transposed_weights_of(weights[i], meta[i][0]) for i in range(n)]
         ctx.save_for_backward(*ws, *xs, *[ys[i] if meta[i][2] == 1 else xs[i].new_empty(0) for i in range(n)])
@@ -202,54 +258,21 @@ class _GroupConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dys):
-        lib = _lib.lib()
         n = len(ctx.meta)
-        saved = ctx.saved_tensors
-        ws, xs, ysv = saved[:n], saved[n:2 * n], saved[2 * n:3 * n]
-        B = xs[0].shape[0]
-        stream = _lib.current_stream()
-        arr = (_lib.ConvDesc * n)()
-        out = [None]
-        keep = []
-        any_launch = False
+        saved = ctx.saved_tensors   # n weights, n inputs, n outputs (empty where the forward fused no ReLU)
+        need = ctx.needs_input_grad
+        probs = []
         for i in range(n):
             stride, pad, relu = ctx.meta[i]
-            w, x = ws[i], xs[i]
             weight, bias = ctx.params[i]
-            cout, cin, k, _ = w.shape
-            need_x, need_w, need_b = ctx.needs_input_grad[1 + 3 * i], ctx.needs_input_grad[2 + 3 * i], ctx.needs_input_grad[3 + 3 * i] and bias is not None
-            dy = dys[i]
-            dy = torch.zeros(ctx.yshapes[i], dtype=torch.float32, device=w.device).contiguous(memory_format=torch.channels_last) if dy is None else _nhwc(dy)
-            if relu:
-                g = torch.empty_like(dy, memory_format=torch.channels_last)
-                _lib.check(lib.ssdk_relu_bwd(_dp(ysv[i]), _dp(dy), dy.numel(), _dp(g), stream), 'ssdk_relu_bwd')
-                dy = g
-            keep.append(dy)
-            defer = (_defer_wgrad and (need_w or need_b) and weight.is_leaf and (bias is None or bias.is_leaf) and not _has_hooks(weight) and not _has_hooks(bias))
-            dw = db = None
-            if need_w and not defer:
-                dw = grad_sink(weight)
-                if dw is None or dw.stride() != w.stride():
-                    dw = torch.empty_like(w, memory_format=torch.channels_last)
-            if need_b and not defer:
-                db = grad_sink(bias)
-                if db is None:
-                    db = torch.empty((cout,), dtype=torch.float32, device=w.device)
-            dx = torch.empty_like(x, memory_format=torch.channels_last) if need_x else None
-            d = arr[i]
-            d.x, d.hin, d.win, d.cin = _dp(x), x.shape[2], x.shape[3], cin
-            d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = _dp(w), None, cout, k, stride, pad, 0
-            d.dy, d.dx, d.dw, d.db = _dp(dy), _dp(dx), _dp(dw), _dp(db)
-            d.w_t = _dp(ctx.w_ts[i])
-            any_launch = any_launch or dx is not None or dw is not None or db is not None
-            if defer:
-                _queue_deferred_wgrad(dict(x=x, dy=dy, w=w, weight=weight if need_w else None, bias=bias if need_b else None, stride=stride, pad=pad))
-            out += [dx, dw, db]
-        if any_launch:
-            _conv2d_bwd(lib, arr, n, B, ws[0].device, stream)
+            need_w, need_b = need[2 + 3 * i], need[3 + 3 * i] and bias is not None
+            defer = (need_w or need_b) and _may_defer(weight, bias)
+            probs.append((saved[i], weight, bias, need_w, need_b, defer, saved[n + i], saved[2 * n + i] if relu else None, dys[i], ctx.yshapes[i],
+                          stride, pad, need[1 + 3 * i], ctx.w_ts[i], None))
+        grads, _ = _conv_backward(probs, shared=False)
         for weight, _ in ctx.params:
             _forget_transposed_weights(weight)
-        return tuple(out)
+        return (None, *grads)
 
 
 def _queue_deferred_wgrad(job):
@@ -298,8 +321,7 @@ def conv2d_bn_group(xs, blocks):
         elif c is None:
             out.append(batch_norm(y, bn, relu=has_act) if type(bn) is torch.nn.BatchNorm2d else (torch.relu(bn(y)) if has_act else bn(y)))
         else:
-            out.append(_BatchNormFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
-                                          True, int(has_act), c, True))
+            out.append(_norm_of_ready_sums(y, bn, c, int(has_act)))
     return out
 
 
@@ -370,8 +392,6 @@ def prepare_weight_transposes(module):
     identity and version, so a stale one is never used: after an optimizer step (or for a convolution that was not prepared) the
     backward simply re-lays out its own weights as before.  No-op when gradients are off.  The entries only carry the layout from this
     call to the backward pass of the forward pass it precedes: the next call makes new ones."""
-    import weakref
-    import ctypes
     if not torch.is_grad_enabled():
         return 0
     convs = [m for m in module.modules() if isinstance(m, torch.nn.Conv2d) and m.groups == 1 and m.weight.is_cuda and m.weight.requires_grad
@@ -400,9 +420,7 @@ def prepare_weight_transposes(module):
         arr = (_lib.ConvDesc * len(group))()
         outs = (ctypes.c_void_p * len(group))()
         for i, (w, k, stride) in enumerate(group):
-            cout, cin = w.shape[0], w.shape[1]
-            d = arr[i]
-            d.w, d.cin, d.cout, d.ksize, d.stride = w.data_ptr(), cin, cout, k, stride
+            _set_desc(arr[i], 0, 0, w.shape[1], w.shape[0], k, stride, 0, w=w)   # (the re-layout reads the weight and its geometry only)
             view = arena[off:off + w.numel()]
             off += sizes[first + i]
             outs[i] = view.data_ptr()
@@ -512,19 +530,8 @@ def _flush_jobs(jobs):
             for i, j in enumerate(grp):
                 w, x = j['w'], j['x']
                 cout, cin, k, _ = w.shape
-                dw = db = None
-                if j['weight'] is not None:
-                    dw = grad_sink(j['weight'])
-                    if dw is None or dw.stride() != w.stride():
-                        dw = torch.empty_like(w, memory_format=torch.channels_last)
-                if j['bias'] is not None:
-                    db = grad_sink(j['bias'])
-                    if db is None:
-                        db = torch.empty((cout,), dtype=torch.float32, device=w.device)
-                d = arr[i]
-                d.x, d.hin, d.win, d.cin = _dp(x), x.shape[2], x.shape[3], cin
-                d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = _dp(w), None, cout, k, j['stride'], j['pad'], 0
-                d.dy, d.dx, d.dw, d.db = _dp(j['dy']), None, _dp(dw), _dp(db)
+                dw, db = _grad_targets(w, j['weight'], j['bias'], j['weight'] is not None, j['bias'] is not None)
+                _set_desc(arr[i], x.shape[2], x.shape[3], cin, cout, k, j['stride'], j['pad'], x, w, dy=j['dy'], dw=dw, db=db)
                 outs.append((j['weight'], dw, j['bias'], db))
             B = grp[0]['x'].shape[0]
             need = lib.ssdk_conv2d_bwd_workspace_bytes(arr, len(grp), B)
@@ -547,10 +554,10 @@ def conv2d(xs, weight, bias=None, stride=1, padding=0, relu=False):
     return out[0] if single else list(out)
 
 
-_NO_FUSED_STATS = bool(__import__('os').environ.get('SSDK_NO_FUSED_STATS'))   # (measurement knob)
-_NO_BN_CHAIN = bool(__import__('os').environ.get('SSDK_NO_BN_CHAIN'))         # (measurement knob: every norm call zero-fills a scratch workspace)
-_NO_RELU_BY_NORM = bool(__import__('os').environ.get('SSDK_NO_RELU_BY_NORM'))   # (measurement knob)
-_NO_DX_ZERO_BY_NORM = bool(__import__('os').environ.get('SSDK_NO_DX_ZERO_BY_NORM'))   # (measurement knob: the convolution zero-fills its own dx)
+_NO_FUSED_STATS = bool(os.environ.get('SSDK_NO_FUSED_STATS'))   # (measurement knob)
+_NO_BN_CHAIN = bool(os.environ.get('SSDK_NO_BN_CHAIN'))         # (measurement knob: every norm call zero-fills a scratch workspace)
+_NO_RELU_BY_NORM = bool(os.environ.get('SSDK_NO_RELU_BY_NORM'))   # (measurement knob)
+_NO_DX_ZERO_BY_NORM = bool(os.environ.get('SSDK_NO_DX_ZERO_BY_NORM'))   # (measurement knob: the convolution zero-fills its own dx)
 fused_stats_calls = 0   # (norm layers whose forward statistics were handed to a convolution's epilogue; tests read it)
 
 
@@ -559,10 +566,23 @@ def _local_training_chain(bn, device):
     training mode, per-process statistics, its forward buffer known to hold zeros.  None otherwise."""
     if _NO_FUSED_STATS or type(bn) is not torch.nn.BatchNorm2d or not bn.training or bn.momentum is None or not bn.track_running_stats or sync_group_of(bn) is not None:
         return None
+    chain = _sums_chain_of(bn, device)
+    return chain if chain.usable(0, device) else None
+
+
+def _sums_chain_of(bn, device):
+    """The layer's _SumsChain on ``device`` (made on first use, and again when the layer moved or changed its width)."""
     chain = getattr(bn, '_ssdk_sums_chain', None)
     if chain is None or chain.buf.device != device or chain.buf.shape[1] != 2 * bn.num_features + 2:
         chain = bn._ssdk_sums_chain = _SumsChain(bn.num_features, device)
-    return chain if chain.usable(0, device) else None
+    return chain
+
+
+def _norm_of_ready_sums(y, bn, chain, relu, link=None):
+    """Training-mode BatchNorm of ``y`` whose statistics the producing convolution has left in chain.buf[0]: ONE apply launch.  relu: the
+    flags of _BatchNormFn;  link: the _DxLink shared with that convolution, or None."""
+    return _BatchNormFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                              True, relu, chain, True, link)
 
 
 def conv2d_batch_norm(xs, weight, bias, stride, padding, bns, conv_relu=False, bn_relu=False):
@@ -596,8 +616,7 @@ def conv2d_batch_norm(xs, weight, bias, stride, padding, bns, conv_relu=False, b
         if c is None:
             out.append(batch_norm(y, bn, relu=bn_relu))
         else:
-            out.append(_BatchNormFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
-                                          True, int(bool(bn_relu)) | (2 if relu_by_norm else 0), c, True, link))
+            out.append(_norm_of_ready_sums(y, bn, c, int(bool(bn_relu)) | (2 if relu_by_norm else 0), link))
     return out[0] if single else out
 
 
@@ -615,12 +634,11 @@ class _DxLink(object):
         self.needs_dx = False
 
     def describe(self, x, cout, ksize, stride, pad, needs_dx):
-        d = self.desc = _lib.ConvDesc()
-        d.hin, d.win, d.cin, d.cout, d.ksize, d.stride, d.pad = x.shape[2], x.shape[3], x.shape[1], cout, ksize, stride, pad
+        self.desc = _lib.ConvDesc()
+        _set_desc(self.desc, x.shape[2], x.shape[3], x.shape[1], cout, ksize, stride, pad)
         self.shape, self.needs_dx = tuple(x.shape), bool(needs_dx)
 
     def _scatter(self):
-        import ctypes
         return self.desc is not None and _lib.lib().ssdk_conv2d_dx_form(ctypes.byref(self.desc)) == 1
 
     def offer(self, device):
@@ -729,11 +747,7 @@ def batch_norm(x, bn, relu=False):
     nbt = bn.num_batches_tracked   # incremented inside the library's launch (torch: a launch of its own per layer)
     if nbt is not None:
         assert nbt.dtype == torch.int64 and nbt.is_cuda
-    chain = None
-    if training and x.is_cuda:
-        chain = getattr(bn, '_ssdk_sums_chain', None)
-        if chain is None or chain.buf.device != x.device or chain.buf.shape[1] != 2 * bn.num_features + 2:
-            chain = bn._ssdk_sums_chain = _SumsChain(bn.num_features, x.device)
+    chain = _sums_chain_of(bn, x.device) if training and x.is_cuda else None
     return _BatchNormFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, nbt, bn.momentum, bn.eps, training, relu, chain, False)
 
 
@@ -987,7 +1001,6 @@ class _SfamFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, n_scales, n_pieces, *flat):
-        import ctypes
         lib = _lib.lib()
         stream = _lib.current_stream()
         pieces = [[_nhwc(flat[s * n_pieces + k]) for k in range(n_pieces)] for s in range(n_scales)]
@@ -1013,11 +1026,8 @@ class _SfamFn(torch.autograd.Function):
             _lib.check(lib.ssdk_sfam_pool_fwd(ptrs[s], n_pieces, B, hw[s], Cp, pooled[s].data_ptr(), stream), 'ssdk_sfam_pool_fwd')
         for x, w, b, y, relu in ((pooled, w1, b1, hidden, 1), (hidden, w2, b2, z, 0)):   # fc1 + F.relu, fc2: one grouped launch each
             arr = (_lib.ConvDesc * n_scales)()
-            for s in range(n_scales):
-                d = arr[s]
-                d.x, d.hin, d.win, d.cin = x[s].data_ptr(), 1, 1, x.shape[2]
-                d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = w[s].data_ptr(), _dp(b[s]), y.shape[2], 1, 1, 0, relu
-                d.y = y[s].data_ptr()
+            for s in range(n_scales):   # (a [B, C] row block is a batch of 1 x 1 maps)
+                _set_desc(arr[s], 1, 1, x.shape[2], y.shape[2], 1, 1, 0, x=x[s], w=w[s], bias=b[s], relu=relu, y=y[s])
             _conv2d_fwd(lib, arr, n_scales, B, dev)
         outs = []
         for s in range(n_scales):
@@ -1031,7 +1041,6 @@ class _SfamFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
-        import ctypes
         lib = _lib.lib()
         stream = _lib.current_stream()
         n_scales, n_pieces, has_b1, has_b2 = ctx.meta
@@ -1045,8 +1054,7 @@ class _SfamFn(torch.autograd.Function):
         dev = pooled.device
         hw = [pieces[s][0].shape[2] * pieces[s][0].shape[3] for s in range(n_scales)]
         ptrs = [(ctypes.c_void_p * n_pieces)(*[p.data_ptr() for p in pieces[s]]) for s in range(n_scales)]
-        douts = [torch.zeros((B, C) + tuple(pieces[s][0].shape[2:]), dtype=torch.float32, device=dev).contiguous(memory_format=torch.channels_last)
-                 if g is None else _nhwc(g) for s, g in enumerate(douts)]
+        douts = [_upstream_grad(g, (B, C) + tuple(pieces[s][0].shape[2:]), dev) for s, g in enumerate(douts)]
         # 1. dz = sigmoid'(z) * sum_hw dout * piece
         dz = torch.empty_like(z)
         for s in range(n_scales):
@@ -1063,10 +1071,7 @@ class _SfamFn(torch.autograd.Function):
         def conv_bwd(x, w, dy, dx, dw, db):
             arr = (_lib.ConvDesc * n_scales)()
             for s in range(n_scales):
-                d = arr[s]
-                d.x, d.hin, d.win, d.cin = x[s].data_ptr(), 1, 1, x.shape[2]
-                d.w, d.bias, d.cout, d.ksize, d.stride, d.pad, d.relu = w[s].data_ptr(), None, dy.shape[2], 1, 1, 0, 0
-                d.dy, d.dx, d.dw, d.db = dy[s].data_ptr(), dx[s].data_ptr(), dw[s].data_ptr(), _dp(db[s])
+                _set_desc(arr[s], 1, 1, x.shape[2], dy.shape[2], 1, 1, 0, x=x[s], w=w[s], dy=dy[s], dx=dx[s], dw=dw[s], db=db[s])
             _conv2d_bwd(lib, arr, n_scales, B, dev, stream)
         conv_bwd(hidden, w2, dz, d_hidden, dw2, db2)
         g_hidden = torch.empty_like(d_hidden)
@@ -1133,8 +1138,7 @@ class _DepthwiseFn(torch.autograd.Function):
         k = weight.shape[-1]
         w = weight.float().contiguous()
         b = None if bias is None else bias.float().contiguous()
-        ho, wo = _out_dim(H, k, stride, pad), _out_dim(W, k, stride, pad)
-        y = torch.empty((B, C, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        y = _conv_out(x, C, k, stride, pad)
         if stats is None:
             _lib.check(lib.ssdk_depthwise_conv2d_fwd(_dp(x), _dp(w), _dp(b), B, H, W, C, k, stride, pad, _dp(y), _lib.current_stream()),
                        'ssdk_depthwise_conv2d_fwd')
@@ -1169,7 +1173,6 @@ class _DepthwiseGroupFn(torch.autograd.Function):
 
     @staticmethod
     def _levels(xs):
-        import ctypes
         n = len(xs)
         hs = (ctypes.c_int * n)(*[x.shape[2] for x in xs])
         ws = (ctypes.c_int * n)(*[x.shape[3] for x in xs])
@@ -1177,7 +1180,6 @@ class _DepthwiseGroupFn(torch.autograd.Function):
 
     @staticmethod
     def _ptrs(ts):
-        import ctypes
         return (ctypes.c_void_p * len(ts))(*[_dp(t) for t in ts])
 
     @staticmethod
@@ -1191,8 +1193,7 @@ class _DepthwiseGroupFn(torch.autograd.Function):
         k = weight.shape[-1]
         w = weight.float().contiguous()
         b = None if bias is None else bias.float().contiguous()
-        ys = [torch.empty((B, C, _out_dim(x.shape[2], k, stride, pad), _out_dim(x.shape[3], k, stride, pad)), dtype=torch.float32, device=x.device,
-                          memory_format=torch.channels_last) for x in xs]
+        ys = [_conv_out(x, C, k, stride, pad) for x in xs]
         n, hs, ws = _DepthwiseGroupFn._levels(xs)
         _lib.check(lib.ssdk_depthwise_conv2d_group_fwd(_DepthwiseGroupFn._ptrs(xs), hs, ws, n, _dp(w), _dp(b), B, C, k, stride, pad,
                                                        _DepthwiseGroupFn._ptrs(ys), _lib.current_stream()), 'ssdk_depthwise_conv2d_group_fwd')
@@ -1208,8 +1209,7 @@ class _DepthwiseGroupFn(torch.autograd.Function):
         B, C = xs[0].shape[:2]
         k = w.shape[-1]
         n, hs, ws = _DepthwiseGroupFn._levels(xs)
-        dys = [torch.zeros((B, C, _out_dim(x.shape[2], k, stride, pad), _out_dim(x.shape[3], k, stride, pad)), dtype=torch.float32, device=x.device,
-                           memory_format=torch.channels_last) if dy is None else _nhwc(dy) for x, dy in zip(xs, dys)]
+        dys = [_conv_out(x, C, k, stride, pad).zero_() if dy is None else _nhwc(dy) for x, dy in zip(xs, dys)]   # (None: a level nobody used)
         dxs = [torch.empty_like(x, memory_format=torch.channels_last) if need else None for x, need in zip(xs, ctx.needs_input_grad[4:])]
         want_w = ctx.needs_input_grad[0] or (has_bias and ctx.needs_input_grad[1])
         dw = torch.empty_like(w) if want_w else None
@@ -1252,8 +1252,7 @@ def depthwise_conv2d_batch_norm(x, weight, bias, stride, padding, bn, relu=False
         chain.clean[0] = False   # (handed to the stencil: whatever happens next, it no longer holds zeros)
         fused_stats_calls += 1
         y = _DepthwiseFn.apply(x, weight, bias, stride, padding, chain.buf[0].data_ptr())
-        return _BatchNormFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
-                                  True, int(bool(relu)), chain, True, None)
+        return _norm_of_ready_sums(y, bn, chain, int(bool(relu)))
     if (plain and not _NO_FUSED_STATS and not bn.training and bn.momentum is not None and bn.track_running_stats
             and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, bn.weight, bn.bias)))):
         lib = _lib.lib()
@@ -1263,8 +1262,7 @@ def depthwise_conv2d_batch_norm(x, weight, bias, stride, padding, bn, relu=False
         k = weight.shape[-1]
         w = weight.detach().float().contiguous()
         b, g, be = [None if t is None else t.detach().float().contiguous() for t in (bias, bn.weight, bn.bias)]
-        y = torch.empty((B, C, _out_dim(H, k, stride, padding), _out_dim(W, k, stride, padding)), dtype=torch.float32, device=x.device,
-                        memory_format=torch.channels_last)
+        y = _conv_out(x, C, k, stride, padding)
         _lib.check(lib.ssdk_depthwise_conv2d_norm_fwd(_dp(x), _dp(w), _dp(b), B, H, W, C, k, stride, padding, _dp(g), _dp(be), _dp(bn.running_mean),
                                                       _dp(bn.running_var), float(bn.eps), int(bool(relu)), _dp(y), _lib.current_stream()),
                    'ssdk_depthwise_conv2d_norm_fwd')
@@ -1275,7 +1273,7 @@ def depthwise_conv2d_batch_norm(x, weight, bias, stride, padding, bn, relu=False
 # Above this many float4 elements of output the statistics stay a pass of their own: on the 63 x 63 x 256 map at batch 32 (8.1 M float4) the
 # stencil + bn_reduce pair takes 304 us and the fused launch 325; at 32 x 32 (2.1 M) they tie at 95 us, below it the fused launch wins
 # (16 x 16: 32 against 36 us) -- profiles/fpnlite_kernel_stats.md.  SSDK_DW_STATS_MAX_N4 overrides (measurement knob).
-_DW_STATS_MAX_N4 = int(__import__('os').environ.get('SSDK_DW_STATS_MAX_N4') or (1 << 21))
+_DW_STATS_MAX_N4 = int(os.environ.get('SSDK_DW_STATS_MAX_N4') or (1 << 21))
 
 
 def _dw_stats_fused(x, weight, stride, padding):
@@ -1337,7 +1335,6 @@ class _ConcatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, *xs):
-        import ctypes
         _lib.require_cuda(*xs)
         xs = [_nhwc(x) for x in xs]
         B, _, H, W = xs[0].shape
@@ -1352,7 +1349,6 @@ class _ConcatFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         dout = _nhwc(dout)
         B, _, H, W = dout.shape
         ds = [torch.empty(s, dtype=torch.float32, device=dout.device, memory_format=torch.channels_last) for s in ctx.shapes]

@@ -486,6 +486,70 @@ def test_deferred_weight_gradients_equal_immediate_ones():
     assert not ops._pending_wgrads
 
 
+def _assert_deferred_equal_immediate(dx_a, dx_b, mod_a, mod_b):
+    """The tolerances of test_deferred_weight_gradients_equal_immediate_ones: a = immediate, b = deferred."""
+    from single_shot_detection_amd import ops
+    for i, (ga, gb) in enumerate(zip(dx_a, dx_b)):
+        np.testing.assert_allclose(gb.cpu().numpy(), ga.cpu().numpy(), rtol=1e-4, atol=1e-5 * float(ga.abs().max()), err_msg=f'dx{i}')
+    for (n1, p1), (n2, p2) in zip(sorted(mod_a.named_parameters()), sorted(mod_b.named_parameters())):
+        assert n1 == n2 and p1.grad is not None and p2.grad is not None, n1
+        np.testing.assert_allclose(p2.grad.cpu().numpy(), p1.grad.cpu().numpy(), rtol=2e-4, atol=2e-5 * float(p1.grad.abs().max()) + 1e-7, err_msg=n1)
+    assert not ops._pending_wgrads
+
+
+def test_deferred_weight_gradients_through_the_grouped_calls_equal_immediate_ones():
+    """Deferral through _GroupConvFn: ops.conv2d_bn_group on three independent Conv2dBn blocks (own kernel size, stride, map), then
+    ops.conv2d_group (biased 1 x 1 convolutions + ReLU) on two of their outputs.  Input gradients and every parameter's .grad after two
+    backward passes (the second accumulates) are those of the immediate path, and no job is left behind."""
+    import copy
+    from single_shot_detection_amd import ops
+    rng = np.random.default_rng(41)
+    mod = nn.ModuleDict({'blocks': nn.ModuleList([conv.Conv2dBn(8, 16, kernel_size=3, stride=1, padding=1),
+                                                  conv.Conv2dBn(16, 8, kernel_size=1),
+                                                  conv.Conv2dBn(8, 8, kernel_size=3, stride=2, padding=1)]),
+                         'fcs': nn.ModuleList([nn.Conv2d(8, 8, 1, bias=True), nn.Conv2d(8, 8, 1, bias=True)])})
+    _randomize(mod, rng)
+    a, b = copy.deepcopy(mod).cuda().train(), copy.deepcopy(mod).cuda().train()
+    xs_np = [rng.standard_normal(s, dtype=np.float32) for s in ((2, 8, 5, 5), (2, 16, 5, 5), (2, 8, 7, 7))]
+
+    def run(m, defer):
+        prev = ops.defer_weight_gradients(defer)
+        try:
+            for _ in range(2):
+                xs = [torch.from_numpy(x).cuda().requires_grad_(True) for x in xs_np]
+                ys = ops.conv2d_bn_group(xs, list(m['blocks']))
+                zs = ops.conv2d_group(ys[1:], list(m['fcs']), relu=True)
+                assert [tuple(t.shape) for t in ys + zs] == [(2, 16, 5, 5), (2, 8, 5, 5), (2, 8, 4, 4), (2, 8, 5, 5), (2, 8, 4, 4)]
+                sum((o * o).sum() for o in ys + zs).backward()
+        finally:
+            ops.defer_weight_gradients(prev)
+        return [x.grad for x in xs]
+
+    _assert_deferred_equal_immediate(run(a, False), run(b, True), a, b)
+
+
+def test_one_flush_of_deferred_weight_gradients_with_two_batch_sizes():
+    """Two Conv2dBn blocks fed maps of batch 2 and batch 3 in ONE backward pass under ops.deferred_weight_gradients(): a grouped call
+    shares the batch size, so the flush has to split its group -- and still delivers the immediate path's gradients."""
+    import copy
+    from single_shot_detection_amd import ops
+    rng = np.random.default_rng(43)
+    mod = nn.ModuleList([conv.Conv2dBn(8, 8, kernel_size=3, padding=1), conv.Conv2dBn(8, 8, kernel_size=3, padding=1)])
+    _randomize(mod, rng)
+    a, b = copy.deepcopy(mod).cuda().train(), copy.deepcopy(mod).cuda().train()
+    xs_np = [rng.standard_normal((batch, 8, 4, 4), dtype=np.float32) for batch in (2, 3)]
+
+    def run(m):
+        xs = [torch.from_numpy(x).cuda().requires_grad_(True) for x in xs_np]
+        sum((blk(x) ** 2).sum() for blk, x in zip(m, xs)).backward()
+        return [x.grad for x in xs]
+
+    dx_a = run(a)
+    with ops.deferred_weight_gradients():
+        dx_b = run(b)
+    _assert_deferred_equal_immediate(dx_a, dx_b, a, b)
+
+
 def test_deferred_weight_gradients_survive_a_backward_pass_that_raised():
     """A backward pass that raises drops autograd's end-of-pass callbacks: the deferred jobs it queued must neither block the next pass's
     flush nor be added into the next step's gradients; a weight with a tensor hook is never deferred (the hook must fire)."""
