@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 123
+#define SSDK_VERSION 124
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -194,6 +194,30 @@ int ssdk_encode_ground_truth_ex(const float* gt_rows, int gt_stride, const int32
                                 const float* anchors, int num_anchors, float matched_threshold, float unmatched_threshold,
                                 int force_match, float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes,
                                 void* stream);
+
+#define SSDK_ATSS_MAX_LEVELS 16
+#define SSDK_ATSS_MAX_TOPK 32
+size_t ssdk_encode_ground_truth_atss_workspace_bytes(int batch, int total_gt, int n_levels);
+/*
+ * Target assignment by Adaptive Training Sample Selection (arXiv:1912.02424, Algorithm 1; the reference has no such assigner).  Inputs and
+ * outputs as for ssdk_encode_ground_truth, without thresholds:
+ *   level_sizes HOST int32 [n_levels], positive, summing to num_anchors: pyramid level l owns the next level_sizes[l] anchors.  Read during
+ *               the call (the kernels get the table by value), so the call may sit in a captured HIP graph.
+ *   topk        candidates per (box, level), 1..SSDK_ATSS_MAX_TOPK; n_levels 1..SSDK_ATSS_MAX_LEVELS.
+ * For every box g = (x1, y1, x2, y2, ...) of an image, all box arithmetic in fp32, one operation at a time:
+ *   1. gcx = (x1 + x2) * 0.5f, gcy = (y1 + y2) * 0.5f; d2(a) = (cx_a - gcx)^2 + (cy_a - gcy)^2.
+ *   2. Candidates: per level the min(topk, level size) anchors of smallest d2, ties to the lower anchor index, a NaN distance last.
+ *   3. t_g = (float)(mean + std) of the n candidates' IoUs (the IoU of ssdk_encode_ground_truth), accumulated in fp64: mean = sum v / n,
+ *      std = sqrt(sum (v - mean)^2 / (n - 1)), 0 when n == 1.
+ *   4. A candidate a qualifies when iou(a, g) >= t_g and x1 < cx_a < x2 and y1 < cy_a < y2 (NaN never qualifies).
+ *   5. An anchor that qualifies for several boxes takes the largest IoU, then the lowest box index.
+ * box_idx[a] is that box or SSDK_NOT_MATCHED: no ignore band and NO force stage -- a box none of whose candidates qualifies has no positive
+ * anchor.  Target rows: the box's six columns for a matched anchor, (0, 0, 0, 0, 0, 1) for every other.  Two launches, no host
+ * synchronisation, the same bits run to run.
+ */
+int ssdk_encode_ground_truth_atss(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                  const float* anchors, int num_anchors, const int32_t* level_sizes, int n_levels, int topk,
+                                  float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- sampler + loss (S1 + L1 + L2 + L3) ----------------------------------------------------------------------- */
 

@@ -17,6 +17,9 @@
 //                         algorithmic minimum for this path.
 // Opt-in (ssdk_encode_ground_truth_ex, SSDK_FORCE_MATCH_BIPARTITE): bipartite_resolve_kernel between the two, one workgroup per image,
 // replaces the force-match rule by greedy bipartite matching (matcher.py:7-31); see further down.
+// Beside it (ssdk_encode_ground_truth_atss; not in the reference): Adaptive Training Sample Selection, two launches of its own --
+// atss_candidates_kernel (one workgroup per (box, level): the level's k nearest anchors as a cutoff key, their IoUs) and
+// atss_assign_kernel (assign_kernel's shape with the box's own threshold in place of the two fixed ones); see further down.
 // IoU is computed op for op like the reference (this TU is built -ffp-contract=off, IEEE divide) so that
 // assignments are bit-exact.
 #include "common.h"
@@ -78,6 +81,29 @@ __global__ void __launch_bounds__(kArgmaxThreads) gt_argmax_kernel(const float* 
     }
 }
 
+// The end of both assign kernels: the thread's target row (box `bi` of the image whose rows start at g0, or the background / ignore row)
+// goes to the LDS tile `s_out` [kAssignThreads * 6], then the block's rows leave as one contiguous run of 8-byte lanes.
+__device__ __forceinline__ void write_target_rows(const float* __restrict__ gt_rows, int gt_stride, int g0, int bi, int i, int a0, int A,
+                                                  float* s_out, float* __restrict__ target, int32_t* __restrict__ box_idx) {
+    const int a = a0 + threadIdx.x;
+    float* o = s_out + threadIdx.x * 6;
+    if (bi >= 0) {  // target_assigner.py:52-54
+        const float* r = gt_rows + (size_t)(g0 + bi) * gt_stride;
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = r[5];
+    } else {
+        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
+        o[4] = bi == SSDK_IGNORE ? -1.0f : 0.0f;  // :56-58 / :39
+        o[5] = bi == SSDK_IGNORE ? -1.0f : 1.0f;  // :40
+    }
+    if (box_idx && a < A) box_idx[(size_t)i * A + a] = bi;
+    __syncthreads();
+    // 24-byte rows of this block are one contiguous run in HBM; (i*A + a0)*24 is always 8-byte aligned.
+    const int rows = min(kAssignThreads, A - a0);
+    float2* dst = reinterpret_cast<float2*>(target + ((size_t)i * A + a0) * 6);
+    const float2* src = reinterpret_cast<const float2*>(s_out);
+    for (int t = threadIdx.x; t < rows * 3; t += kAssignThreads) dst[t] = src[t];
+}
+
 __global__ void __launch_bounds__(kAssignThreads) assign_kernel(const float* __restrict__ gt_rows, int gt_stride,
                                                                 const int32_t* __restrict__ gt_off,
                                                                 const float4* __restrict__ anchors, int A, float matched_thr,
@@ -127,22 +153,7 @@ __global__ void __launch_bounds__(kAssignThreads) assign_kernel(const float* __r
         else if (best < matched_thr) bi = SSDK_IGNORE;
         if (forced >= 0) bi = forced;
     }
-    float* o = s_out + threadIdx.x * 6;
-    if (bi >= 0) {  // target_assigner.py:52-54
-        const float* r = gt_rows + (size_t)(g0 + bi) * gt_stride;
-        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3]; o[4] = r[4]; o[5] = r[5];
-    } else {
-        o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f;
-        o[4] = bi == SSDK_IGNORE ? -1.0f : 0.0f;  // :56-58 / :39
-        o[5] = bi == SSDK_IGNORE ? -1.0f : 1.0f;  // :40
-    }
-    if (box_idx && a < A) box_idx[(size_t)i * A + a] = bi;
-    __syncthreads();
-    // 24-byte rows of this block are one contiguous run in HBM; (i*A + a0)*24 is always 8-byte aligned.
-    const int rows = min(kAssignThreads, A - a0);
-    float2* dst = reinterpret_cast<float2*>(target + ((size_t)i * A + a0) * 6);
-    const float2* src = reinterpret_cast<const float2*>(s_out);
-    for (int t = threadIdx.x; t < rows * 3; t += kAssignThreads) dst[t] = src[t];
+    write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
 }
 
 // ---- detection/matcher.py:33-56 on a materialised weight matrix [G, A] (the API the reference exposes; the training path uses the
@@ -383,6 +394,167 @@ __global__ void __launch_bounds__(256) copy_f32_kernel(const float* __restrict__
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
+// ---- Adaptive Training Sample Selection (arXiv:1912.02424, Algorithm 1; not in the reference) ------------------------------------------
+// Per box: the min(k, n_l) anchors of every pyramid level nearest to the box centre are its candidates; mean + unbiased standard deviation
+// of their IoUs (fp64, two passes) is the box's own threshold t_g; a candidate whose IoU reaches t_g and whose centre lies strictly inside
+// the box is positive; an anchor positive for several boxes takes the largest IoU, then the lowest box index.  No ignore band, no force
+// stage.  Two launches, nothing [G, A]-shaped, no atomics, nothing zero-filled, every sum in a fixed order:
+//   1. atss_candidates_kernel  one workgroup per (box, level): ONE sweep of the level's anchors (16-byte loads), every anchor a 64-bit key
+//                              (centre-distance bits << 32 | anchor), smaller = nearer, ties to the lower anchor, a NaN distance last.
+//                              The workgroup pops its kk = min(k, n_l) smallest keys and stores the LAST one -- the level's cutoff key --
+//                              and the kk candidates' IoUs.  No candidate list leaves the kernel.
+//   2. atss_assign_kernel      one thread per (image, anchor), on the pattern of assign_kernel: it re-derives its key against each box of
+//                              the image and is that box's candidate exactly when key <= cutoff(box, its level).  The thread that loads
+//                              a box into LDS finishes t_g from the stored candidate IoUs (level order, then rank order).
+constexpr int kAtssThreads = 1024;
+constexpr int kAtssWaves = kAtssThreads / kWave;
+constexpr unsigned long long kAtssNoKey = ~0ull;   // above every key (an anchor index is below 2^31)
+struct AtssLevels { int n; int off[SSDK_ATSS_MAX_LEVELS + 1]; };   // level l owns anchors [off[l], off[l + 1]); by value: no table to upload
+
+struct OpMinU64 {
+    __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a < b ? a : b; }
+};
+
+// (gcx, gcy) of a box, then an anchor's key against it: two subtractions, two products, one add, all fp32 and uncontracted.  The sum of two
+// squares is never negative, so its bits order like the value; NaN goes above +inf.
+__device__ __forceinline__ float2 atss_centre(float4 gb) { return make_float2((gb.x + gb.z) * 0.5f, (gb.y + gb.w) * 0.5f); }
+__device__ __forceinline__ unsigned long long atss_key(float4 p, float2 gc, int a) {
+    const float dx = p.x - gc.x, dy = p.y - gc.y;
+    const float d2 = dx * dx + dy * dy;
+    const unsigned u = (d2 != d2) ? 0xFFFFFFFFu : __float_as_uint(d2);
+    return ((unsigned long long)u << 32) | (unsigned long long)(unsigned)a;
+}
+
+__global__ void __launch_bounds__(kAtssThreads) atss_candidates_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                       int batch, const float4* __restrict__ anchors, AtssLevels lv, int topk,
+                                                                       unsigned long long* __restrict__ cutoff, float* __restrict__ cand_iou) {
+    __shared__ unsigned long long s_red[2][kAtssWaves];
+    const int g = blockIdx.x, l = blockIdx.y;
+    if (g >= gt_off[batch]) return;   // rows past the last image's are padding (a row buffer of fixed capacity)
+    int a_begin = 0, a_end = 0;
+#pragma unroll
+    for (int q = 0; q < SSDK_ATSS_MAX_LEVELS; ++q)   // (constant indices: a by-value table indexed by a variable would be copied to scratch)
+        if (q == l) { a_begin = lv.off[q]; a_end = lv.off[q + 1]; }
+    const int kk = min(topk, a_end - a_begin);
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const float* r = gt_rows + (size_t)g * gt_stride;
+    const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
+    const float2 gc = atss_centre(gb);
+    // The sweep: the thread's two smallest keys stay in registers.  Its anchors are kAtssThreads apart, the anchors of one cell and of
+    // neighbouring cells are not, so a thread almost never owns more than one of a box's candidates.
+    unsigned long long k1 = kAtssNoKey, k2 = kAtssNoKey;
+    auto take = [&](int a, const float4& p) {
+        const unsigned long long k = atss_key(p, gc, a);
+        const bool lt1 = k < k1, lt2 = k < k2;   // (selects: the branchy form made the compiler keep k1 and k2 in scratch)
+        k2 = lt1 ? k1 : (lt2 ? k : k2);
+        k1 = lt1 ? k : k1;
+    };
+    int a = a_begin + threadIdx.x;
+    for (; a + 3 * kAtssThreads < a_end; a += 4 * kAtssThreads) {   // four loads in flight
+        const float4 p0 = anchors[a], p1 = anchors[a + kAtssThreads], p2 = anchors[a + 2 * kAtssThreads], p3 = anchors[a + 3 * kAtssThreads];
+        take(a, p0);
+        take(a + kAtssThreads, p1);
+        take(a + 2 * kAtssThreads, p2);
+        take(a + 3 * kAtssThreads, p3);
+    }
+    for (; a < a_end; a += kAtssThreads) take(a, anchors[a]);
+    // kk pops of the workgroup's smallest remaining key, one barrier each (the two halves of s_red alternate).  The owner of the popped key
+    // moves on to its second key; only a thread that loses both re-reads its own anchors for the next one above the popped key.
+    unsigned long long cur = k1, mine = kAtssNoKey, popped = 0ull;
+    for (int j = 0; j < kk; ++j) {
+        const unsigned long long w = wave_allreduce(cur, OpMinU64());
+        if (lane == 0) s_red[j & 1][wave] = w;
+        __syncthreads();
+        popped = s_red[j & 1][0];
+#pragma unroll
+        for (int q = 1; q < kAtssWaves; ++q) { const unsigned long long t = s_red[j & 1][q]; popped = t < popped ? t : popped; }
+        if (threadIdx.x == j) mine = popped;   // (kk <= 32: thread j keeps the j-th candidate)
+        if (cur == popped) {
+            if (cur == k1) cur = k2;   // (kAtssNoKey when the thread swept a single anchor: it has nothing left)
+            else {
+                cur = kAtssNoKey;
+                for (int b = a_begin + threadIdx.x; b < a_end; b += kAtssThreads) {
+                    const unsigned long long k = atss_key(anchors[b], gc, b);
+                    if (k > popped && k < cur) cur = k;
+                }
+            }
+        }
+    }
+    if (threadIdx.x < kk) {   // rule 3's v_i, the IoU assign_kernel computes, in rank order
+        const float4 c = to_corners(anchors[min((unsigned)(mine & 0xFFFFFFFFull), (unsigned)(a_end - 1))]);   // (a popped key is always an anchor of the level; the clamp costs nothing)
+        cand_iou[((size_t)g * lv.n + l) * SSDK_ATSS_MAX_TOPK + threadIdx.x] = iou_corner(gb, area4(gb.x, gb.y, gb.z, gb.w), c, area4(c.x, c.y, c.z, c.w));
+    }
+    if (threadIdx.x == 0) cutoff[(size_t)g * lv.n + l] = popped;
+}
+
+__global__ void __launch_bounds__(kAssignThreads) atss_assign_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                     const float4* __restrict__ anchors, int A, AtssLevels lv, int topk,
+                                                                     const unsigned long long* __restrict__ cutoff, const float* __restrict__ cand_iou,
+                                                                     float* __restrict__ target, int32_t* __restrict__ box_idx) {
+    __shared__ float4 s_box[kGtChunk];
+    __shared__ float s_area[kGtChunk];
+    __shared__ float2 s_centre[kGtChunk];
+    __shared__ float s_thr[kGtChunk];
+    __shared__ unsigned long long s_cut[kGtChunk * SSDK_ATSS_MAX_LEVELS];
+    __shared__ __attribute__((aligned(16))) float s_out[kAssignThreads * 6];
+
+    const int i = blockIdx.y;
+    const int a0 = blockIdx.x * kAssignThreads;
+    const int a = a0 + threadIdx.x;
+    const int g0 = gt_off[i], G = gt_off[i + 1] - g0;
+    const int L = lv.n;
+
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), c = p;
+    float carea = 0.f;
+    int l = 0;
+    if (a < A) {
+        p = anchors[a];
+        c = to_corners(p);
+        carea = area4(c.x, c.y, c.z, c.w);
+        while (l + 1 < L && a >= lv.off[l + 1]) ++l;
+    }
+    float best = 0.0f;
+    int bi = SSDK_NOT_MATCHED;
+    for (int base = 0; base < G; base += kGtChunk) {
+        const int n = min(kGtChunk, G - base);
+        __syncthreads();
+        if (threadIdx.x < n) {
+            const int g = g0 + base + threadIdx.x;
+            const float* r = gt_rows + (size_t)g * gt_stride;
+            const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
+            s_box[threadIdx.x] = gb;
+            s_area[threadIdx.x] = area4(gb.x, gb.y, gb.z, gb.w);
+            s_centre[threadIdx.x] = atss_centre(gb);
+            // t_g: fp64, two passes over the box's candidates in (level, rank) order -- the same order in every workgroup
+            const float* v = cand_iou + (size_t)g * L * SSDK_ATSS_MAX_TOPK;
+            double sum = 0.0;
+            int cnt = 0;
+            for (int q = 0; q < L; ++q) {
+                const int kk = min(topk, lv.off[q + 1] - lv.off[q]);
+                for (int j = 0; j < kk; ++j) sum += (double)v[q * SSDK_ATSS_MAX_TOPK + j];
+                cnt += kk;
+            }
+            const double mean = sum / (double)cnt;
+            double dev = 0.0;
+            for (int q = 0; q < L; ++q) {
+                const int kk = min(topk, lv.off[q + 1] - lv.off[q]);
+                for (int j = 0; j < kk; ++j) { const double d = (double)v[q * SSDK_ATSS_MAX_TOPK + j] - mean; dev += d * d; }
+            }
+            s_thr[threadIdx.x] = (float)(mean + (cnt > 1 ? sqrt(dev / (double)(cnt - 1)) : 0.0));
+        }
+        for (int t = threadIdx.x; t < n * L; t += kAssignThreads) s_cut[t] = cutoff[(size_t)(g0 + base) * L + t];
+        __syncthreads();
+        for (int k = 0; k < n; ++k) {
+            if (atss_key(p, s_centre[k], a) > s_cut[k * L + l]) continue;   // not among the box's nearest on this level
+            const float4 gb = s_box[k];
+            const float v = iou_corner(gb, s_area[k], c, carea);
+            const bool inside = gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w;
+            if (inside && v >= s_thr[k] && (bi < 0 || v > best)) { best = v; bi = base + k; }   // ascending k, strict >: the lowest box index keeps a tie
+        }
+    }
+    write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
+}
+
 }  // namespace ssdk
 
 using namespace ssdk;
@@ -533,5 +705,59 @@ extern "C" int ssdk_encode_ground_truth_ex(const float* gt_rows, int gt_stride, 
     hipLaunchKernelGGL(assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
                        num_anchors, matched_threshold, unmatched_threshold, gt_best, segs, target, box_idx);
     SSDK_CHECK_LAUNCH("assign_kernel");
+    return SSDK_OK;
+}
+
+extern "C" size_t ssdk_encode_ground_truth_atss_workspace_bytes(int batch, int total_gt, int n_levels) {
+    (void)batch;
+    const size_t slots = (size_t)(total_gt > 0 ? total_gt : 1) * (size_t)(n_levels > 0 ? n_levels : 1);
+    Carver c(nullptr);
+    c.take<unsigned long long>(slots);
+    c.take<float>(slots * SSDK_ATSS_MAX_TOPK);
+    return c.off;
+}
+
+extern "C" int ssdk_encode_ground_truth_atss(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                             const float* anchors, int num_anchors, const int32_t* level_sizes, int n_levels, int topk,
+                                             float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_atss: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
+    SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: batch exceeds grid limits");
+    SSDK_REQUIRE(gt_offsets && anchors && target && level_sizes && (gt_rows || total_gt == 0), SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_atss: null pointer");
+    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: gt_stride=%d < 6", gt_stride);
+    SSDK_REQUIRE(n_levels >= 1 && n_levels <= SSDK_ATSS_MAX_LEVELS, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: n_levels=%d outside 1..%d",
+                 n_levels, SSDK_ATSS_MAX_LEVELS);
+    SSDK_REQUIRE(topk >= 1 && topk <= SSDK_ATSS_MAX_TOPK, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: topk=%d outside 1..%d", topk,
+                 SSDK_ATSS_MAX_TOPK);
+    AtssLevels lv;
+    lv.n = n_levels;
+    long long sum = 0;
+    for (int l = 0; l <= SSDK_ATSS_MAX_LEVELS; ++l) {
+        lv.off[l] = (int)sum;   // (the entries past n_levels repeat the total)
+        if (l < n_levels) {
+            SSDK_REQUIRE(level_sizes[l] > 0, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: level_sizes[%d]=%d", l, level_sizes[l]);
+            sum += level_sizes[l];
+            SSDK_REQUIRE(sum <= num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: level sizes exceed the %d anchors", num_anchors);
+        }
+    }
+    SSDK_REQUIRE(sum == num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: level sizes sum to %lld, not to the %d anchors", sum,
+                 num_anchors);
+    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_atss_workspace_bytes(batch, total_gt, n_levels), SSDK_E_WORKSPACE,
+                 "ssdk_encode_ground_truth_atss: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t slots = (size_t)(total_gt > 0 ? total_gt : 1) * (size_t)n_levels;
+    Carver c(workspace);
+    unsigned long long* cutoff = c.take<unsigned long long>(slots);
+    float* cand_iou = c.take<float>(slots * SSDK_ATSS_MAX_TOPK);
+    if (total_gt > 0) {
+        hipLaunchKernelGGL(atss_candidates_kernel, dim3(total_gt, n_levels), dim3(kAtssThreads), 0, s, gt_rows, gt_stride, gt_offsets, batch,
+                           (const float4*)anchors, lv, topk, cutoff, cand_iou);
+        SSDK_CHECK_LAUNCH("atss_candidates_kernel");
+    }
+    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
+    hipLaunchKernelGGL(atss_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors, lv,
+                       topk, cutoff, cand_iou, target, box_idx);
+    SSDK_CHECK_LAUNCH("atss_assign_kernel");
     return SSDK_OK;
 }

@@ -57,13 +57,22 @@ class Detector(nn.Module):
         self.predictor = Predictor(*args)
         self.priors = anchor_generators
         self._anchor_cache = {}
+        self._anchor_levels = {}
 
     def generate_anchors(self, img, sources):
         key = (tuple(img.shape[2:]), tuple(tuple(s.shape[2:]) for s in sources), str(img.device))
         if key not in self._anchor_cache:  # detector.py:82-86, once per geometry instead of once per step
             anchors = [g.generate(img, s).reshape(-1) for s, g in zip(sources, self.priors)]
             self._anchor_cache[key] = torch.cat(anchors, dim=0).view(-1, 4)
+            self._anchor_levels[key] = tuple(a.numel() // 4 for a in anchors)
         return self._anchor_cache[key]
+
+    def anchor_level_sizes(self, anchors):
+        """The anchor count of every pyramid level of a tensor ``generate_anchors`` handed out (what ``AtssTargetAssigner`` needs)."""
+        for key, cached in self._anchor_cache.items():
+            if cached is anchors:
+                return self._anchor_levels[key]
+        raise ValueError('anchor_level_sizes: not a tensor this detector generated')
 
     def forward(self, img):
         scores, locs, locs_sources = self.predictor.forward(img)

@@ -15,7 +15,19 @@ from .box_coder import BoxCoder
 from .detector_wrapper import DetectorWrapper
 from .losses.multibox_loss import MultiboxLoss
 from .postprocessor import Postprocessor
-from .target_assigner import TargetAssigner
+from .target_assigner import AtssTargetAssigner, TargetAssigner
+
+TARGET_ASSIGNERS = {'TargetAssigner': TargetAssigner, 'AtssTargetAssigner': AtssTargetAssigner}
+
+
+def build_target_assigner(args):
+    """A config's ``target_assigner`` dict.  ``'name'`` (not in the reference) picks the class, by default ``'TargetAssigner'``, whose
+    keywords the other entries are: ``{'name': 'AtssTargetAssigner', 'topk': 9}`` is the adaptive assigner."""
+    args = dict(args)
+    name = args.pop('name', 'TargetAssigner')
+    if name not in TARGET_ASSIGNERS:
+        raise ValueError(f'target_assigner: name={name!r}, expected one of {sorted(TARGET_ASSIGNERS)}')
+    return TARGET_ASSIGNERS[name](**args)
 
 
 def init(device, model_args, box_coder_args, postprocess_args, loss_args, sampler_args, target_assigner_args, state={},
@@ -60,8 +72,13 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
     box_coder = BoxCoder(**box_coder_args)
     criterion = MultiboxLoss(sampler=sampler, box_coder=box_coder, **loss_args)
     postprocessor = Postprocessor(box_coder, **postprocess_args)
-    target_assigner = TargetAssigner(**target_assigner_args)
+    target_assigner = build_target_assigner(target_assigner_args)
     detector_wrapper = DetectorWrapper(detector, preprocess, postprocessor)
+
+    def encode_ground_truth(ground_truth, priors):
+        if isinstance(target_assigner, AtssTargetAssigner):   # (it selects per pyramid level)
+            return target_assigner.encode_ground_truth(ground_truth, priors, level_sizes=detector.anchor_level_sizes(priors))
+        return target_assigner.encode_ground_truth(ground_truth, priors)
 
     def init_epoch_state():
         return {'class_loss': 0.0, 'loc_loss': 0.0, 'loss': 0.0}
@@ -85,7 +102,7 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
                 scores, locs, loc_sources = detector.predictor.forward_from_taps(list(t[:n_sources]), t[x_index])
                 priors = detector.generate_anchors(img_like, loc_sources)
                 self.priors = priors
-                target = target_assigner.encode_ground_truth(self.packed, priors)
+                target = encode_ground_truth(self.packed, priors)
                 loss, class_loss, loc_loss = criterion((scores, locs), priors, target)
                 return loss, class_loss, loc_loss, scores, locs
             params = [p for n, p in detector.predictor.named_parameters() if not n.startswith('features.')]
@@ -111,7 +128,7 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
             prediction, priors = [scores, locs], hot.priors
         else:
             *prediction, priors = detector(imgs)
-            target = target_assigner.encode_ground_truth(ground_truth, priors)
+            target = encode_ground_truth(ground_truth, priors)
             loss, class_loss, loc_loss = criterion(prediction, priors, target)
         prediction = [x.detach() for x in prediction]
         if phase == 'eval':

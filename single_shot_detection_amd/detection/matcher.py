@@ -2,7 +2,8 @@
 ``ssdk_encode_ground_truth`` (csrc/match.hip) and no [Boxes, AnchorBoxes] matrix exists; ``match_per_prediction`` below is the
 reference's own function on a given weight matrix (``ssdk_match_per_prediction``), ``match_boxes`` the fused form for one box set.
 ``match_bipartite`` (matcher.py:7-31) is the reference's own function on a given matrix too (``ssdk_match_bipartite``); nothing in the
-reference calls it, here it is also the opt-in force stage of the fused path (``TargetAssigner(force_match='bipartite')``)."""
+reference calls it, here it is also the opt-in force stage of the fused path (``TargetAssigner(force_match='bipartite')``).
+``match_atss`` is the one-image form of ``AtssTargetAssigner`` (``ssdk_encode_ground_truth_atss``), which the reference does not have."""
 import torch
 
 from .. import _lib
@@ -53,6 +54,17 @@ def match_boxes(gt_boxes, anchors, matched_threshold, unmatched_threshold=None, 
     gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
     gt[:, :4] = gt_boxes[:, :4]
     _, idx = TargetAssigner(matched_threshold, unmatched_threshold, force_match).encode_ground_truth([gt], anchors, return_box_idx=True)
+    return idx[0].long()
+
+
+def match_atss(gt_boxes, anchors, level_sizes, topk=9):
+    """box_idx int64 [A] for one image by Adaptive Training Sample Selection (``AtssTargetAssigner``; not in the reference): the box an
+    anchor is positive for, else NOT_MATCHED -- there is no ignore band and no force stage.  ``gt_boxes`` [G, >=4] corner form,
+    ``anchors`` [A,4] centroid, ``level_sizes`` the anchor count of every pyramid level."""
+    from .target_assigner import AtssTargetAssigner
+    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
+    gt[:, :4] = gt_boxes[:, :4]
+    _, idx = AtssTargetAssigner(topk).encode_ground_truth([gt], anchors, return_box_idx=True, level_sizes=level_sizes)
     return idx[0].long()
 
 

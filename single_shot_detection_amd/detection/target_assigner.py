@@ -1,4 +1,7 @@
-"""TargetAssigner -- mirror of detection/target_assigner.py:17-63 on libssdk (csrc/match.hip)."""
+"""TargetAssigner -- mirror of detection/target_assigner.py:17-63 on libssdk (csrc/match.hip); AtssTargetAssigner, the adaptive assigner
+the reference does not have, beside it."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -139,6 +142,58 @@ class TargetAssigner(object):
                                                     float(self.unmatched_threshold), _lib.ptr(target), _lib.ptr(box_idx),
                                                     _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
                        'ssdk_encode_ground_truth')
+        # keep the staging tensors alive until the stream has consumed them
+        target._ssdk_keepalive = (rows, offs)
+        return (target, box_idx) if return_box_idx else target
+
+
+ATSS_MAX_TOPK = 32     # SSDK_ATSS_MAX_TOPK (include/ssdk.h)
+
+
+class AtssTargetAssigner(object):
+    """Adaptive Training Sample Selection (arXiv:1912.02424, Algorithm 1; not in the reference) in place of the two IoU thresholds.  Per
+    ground-truth box the ``topk`` anchors of every pyramid level nearest to the box centre are its candidates; the mean plus the
+    (unbiased) standard deviation of their IoUs is that box's own threshold; a candidate is positive when its IoU reaches the threshold
+    and its centre lies strictly inside the box; an anchor positive for several boxes takes the largest IoU, then the lowest box index.
+    There is no ignore band and NO force stage: a box none of whose candidates qualifies (a sliver between anchor centres) has no
+    positive anchor at all -- that is ATSS.  The exact rule, operation by operation: ``ssdk_encode_ground_truth_atss`` in include/ssdk.h."""
+
+    def __init__(self, topk=9):
+        if int(topk) != topk or not 1 <= topk <= ATSS_MAX_TOPK:
+            raise ValueError(f'AtssTargetAssigner: topk={topk!r}, expected an integer in 1..{ATSS_MAX_TOPK}')
+        self.topk = int(topk)
+        self._ws = None
+        self._levels = {}
+
+    def encode_ground_truth(self, ground_truth, anchors, return_box_idx=False, level_sizes=None):
+        """Inputs and outputs as ``TargetAssigner.encode_ground_truth``; ``level_sizes``: the anchor count of every pyramid level, in the
+        anchors' order (``Detector.anchor_level_sizes(anchors)``)."""
+        num_anchors = anchors.size(0)
+        if level_sizes is None:
+            raise ValueError('AtssTargetAssigner.encode_ground_truth: level_sizes is required (Detector.anchor_level_sizes(anchors))')
+        sizes = tuple(int(n) for n in level_sizes)
+        if sum(sizes) != num_anchors:
+            raise ValueError(f'AtssTargetAssigner.encode_ground_truth: level_sizes sum to {sum(sizes)}, the anchors are {num_anchors}')
+        _lib.require_cuda(anchors)
+        if sizes not in self._levels:
+            self._levels[sizes] = (ctypes.c_int32 * len(sizes))(*sizes)
+        lib = _lib.lib()
+        device = anchors.device
+        batch_size = len(ground_truth)
+        anchors = anchors.contiguous().float()
+        if isinstance(ground_truth, PackedGroundTruth):
+            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
+        else:
+            rows, offs, total = pack_ground_truth(ground_truth, device)
+        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
+        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
+        need = lib.ssdk_encode_ground_truth_atss_workspace_bytes(batch_size, total, len(sizes))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
+        _lib.check(lib.ssdk_encode_ground_truth_atss(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors,
+                                                     self._levels[sizes], len(sizes), self.topk, _lib.ptr(target), _lib.ptr(box_idx),
+                                                     _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
+                   'ssdk_encode_ground_truth_atss')
         # keep the staging tensors alive until the stream has consumed them
         target._ssdk_keepalive = (rows, offs)
         return (target, box_idx) if return_box_idx else target
