@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 124
+#define SSDK_VERSION 125
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -45,6 +45,19 @@ extern "C" {
 #define SSDK_CLS_SOFTMAX_FOCAL 2 /* SoftmaxFocalLoss, losses.py:56-78 */
 #define SSDK_CLS_CE_SOFT 3       /* CrossEntropyWithSoftTargetsLoss, losses.py:80-93 (target of multibox_loss.py:68-71) */
 #define SSDK_CLS_BCE_SOFT 4      /* BinaryCrossEntropyWithSoftTargetsLoss, losses.py:95-106 (target of multibox_loss.py:64-67) */
+/* IoU-aware sigmoid kinds (not in the reference).  For one logit x with target y in [0, 1]: s = 1 / (1 + exp(-x)),
+ * bce(x, y) = max(x, 0) - x y + log1p(exp(-|x|)).  The target row is the multiclass layout of multibox_loss.py:64-67 (the column of
+ * class k is k - 1): a positive row (class not 0 / -1) has y = w * q in its class column and 0 elsewhere, every other sampled row
+ * (a sampled ignore row included) is all zeros.  w = target column 5 (the mixup weight), q = the quality: 1 with
+ * quality_from_iou == 0; otherwise the plain IoU (inter / union, clamped to [0, 1], 0 where the union is not positive or the quotient
+ * not finite) of the prediction's decoded corners (box_coder.py:55-57 + to_corners) against the row's RAW target corners.  q is a
+ * constant of the step: no gradient reaches locs through it. */
+#define SSDK_CLS_QUALITY_FOCAL 5 /* Quality Focal Loss (arXiv:2006.04388), beta = focal_gamma >= 1:
+                                    value |y - s|^beta bce(x, y),
+                                    gradient beta |y - s|^(beta - 1) sgn(s - y) s (1 - s) bce(x, y) + |y - s|^beta (s - y), sgn(0) = 0 */
+#define SSDK_CLS_VARIFOCAL 6     /* Varifocal Loss (arXiv:2008.13367), alpha = focal_alpha in [0, 1], gamma = focal_gamma >= 0:
+                                    y > 0:  value y bce(x, y), gradient y (s - y);
+                                    y == 0: value alpha s^gamma bce(x, 0), gradient alpha s^gamma (gamma (1 - s) bce(x, 0) + s) */
 /* localisation loss kinds */
 #define SSDK_LOC_SMOOTH_L1 0 /* torch.nn.SmoothL1Loss(reduction='sum') on box_coder-encoded targets, multibox_loss.py:81-86 */
 #define SSDK_LOC_GIOU 1      /* GeneralizedIoULoss, losses.py:109-114, on decoded corners (multibox_loss.py:77-79) */
@@ -238,6 +251,9 @@ int ssdk_hard_negative_mining(const float* scores, const float* target_classes, 
 /* detection/sampler.py:9-10 naive_sampler: positives only. */
 int ssdk_naive_sampler(const float* target_classes, int class_stride, int batch, int num_anchors, uint8_t* sampled,
                        void* stream);
+/* Its twin for losses that train the classifier on every anchor: sampled = (class != -1). */
+int ssdk_valid_sampler(const float* target_classes, int class_stride, int batch, int num_anchors, uint8_t* sampled,
+                       void* stream);
 
 /*
  * Loss configuration of detection/losses/multibox_loss.py:11-33 (what the constructed loss objects carry).
@@ -254,6 +270,9 @@ int ssdk_naive_sampler(const float* target_classes, int class_stride, int batch,
  *   torch.nn.functional.cross_entropy.  ce_label_smoothing in [0, 1]; class_weight DEV float[C] or NULL (every w_c = 1), read by the
  *   forward and the backward (keep it alive and at the same address across both -- and across the replays of a captured graph).
  *   Both fields are appended: a positional initialisation of the older fields leaves them 0 / NULL, i.e. plain cross-entropy.
+ *   quality_from_iou (appended likewise, 0 when left out): SSDK_CLS_QUALITY_FOCAL / _VARIFOCAL only -- non-zero computes the quality q
+ *   from the predicted box (above), 0 takes q = 1 (the target value is given).  For these two kinds focal_gamma is beta (>= 1) resp.
+ *   gamma (>= 0), focal_alpha is Varifocal's alpha in [0, 1], and reduce_mean means what it means for the focal kinds.
  */
 typedef struct ssdk_loss_params {
     int cls_kind;  /* SSDK_CLS_* */
@@ -268,6 +287,7 @@ typedef struct ssdk_loss_params {
     float smooth_l1_beta;     /* SmoothL1Loss beta, HuberLoss delta */
     float ce_label_smoothing; /* CrossEntropyLoss label_smoothing */
     const float* class_weight; /* CrossEntropyLoss weight, DEV [C] or NULL */
+    int quality_from_iou;      /* SSDK_CLS_QUALITY_FOCAL / _VARIFOCAL: q = IoU(decoded prediction, raw target) instead of 1 */
 } ssdk_loss_params;
 
 /*
@@ -280,7 +300,12 @@ typedef struct ssdk_loss_params {
  *   out3   DEV float[3] = (loss, class_loss, loc_loss), each already divided by max(1, #positives).
  *   lse_valid != 0: the workspace already holds this batch's per-anchor log-sum-exp (left there by
  *          ssdk_hard_negative_mining on the same scores), so the scores are not read again for sampled negatives.
- * The workspace keeps what ssdk_multibox_loss_bwd needs (divider, scale, per-anchor log-sum-exp); pass the same one.
+ *   sampled DEV uint8 [batch, A], or NULL = "every row whose class is not -1 is sampled" (what ssdk_valid_sampler writes, without
+ *          the mask).  NULL is accepted for SSDK_CLS_SIGMOID_FOCAL, _QUALITY_FOCAL and _VARIFOCAL only (SSDK_E_INVALID otherwise); it
+ *          runs the dense, element-parallel kernels, which _QUALITY_FOCAL and _VARIFOCAL use with a mask as well.
+ * The workspace keeps what ssdk_multibox_loss_bwd needs (divider, scale, per-anchor log-sum-exp -- for SSDK_CLS_QUALITY_FOCAL /
+ * _VARIFOCAL the per-anchor quality q instead, so that the backward sees the forward's q whatever the box kind did to the target);
+ * pass the same one.
  */
 int ssdk_multibox_loss_fwd(const ssdk_loss_params* params, const float* scores, const float* locs, const float* anchors,
                            float* target, const uint8_t* sampled, int batch, int num_anchors, int num_classes, int lse_valid,
@@ -289,7 +314,7 @@ int ssdk_multibox_loss_fwd(const ssdk_loss_params* params, const float* scores, 
 /*
  * Backward of ssdk_multibox_loss_fwd.  grad_out DEV float[2] = (dL/dclass_loss, dL/dloc_loss).
  * target is the target as the forward call left it.  dscores DEV [batch, A, C] and dlocs DEV [batch, A, 4] are
- * written in full (zeros off the sampled / positive rows).
+ * written in full (zeros off the sampled / positive rows).  sampled: the forward call's (NULL included).
  */
 int ssdk_multibox_loss_bwd(const ssdk_loss_params* params, const float* scores, const float* locs, const float* anchors,
                            const float* target, const uint8_t* sampled, const float* grad_out, int batch, int num_anchors,

@@ -58,6 +58,7 @@ _SIGNATURES = {
     'ssdk_hard_negative_mining': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                             C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'ssdk_naive_sampler': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'ssdk_valid_sampler': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'ssdk_multibox_loss_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'ssdk_multibox_loss_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -197,11 +198,21 @@ class HeadLevel(C.Structure):
 
 
 class LossParams(C.Structure):
-    """ssdk_loss_params (include/ssdk.h)."""
+    """ssdk_loss_params (include/ssdk.h).  ``_fields_`` are the fields up to ABI 124; what ABI 125 appended lives in the subclass below,
+    which ctypes lays out behind them, and ``LossParams(...)`` always constructs that full struct -- zero-initialised, so a caller that
+    gives the older fields positionally gets ``quality_from_iou == 0``, and the library never reads past what Python allocated."""
     _fields_ = [('cls_kind', C.c_int), ('loc_kind', C.c_int), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float),
                 ('reduce_mean', C.c_int), ('soft_epsilon', C.c_float), ('classification_weight', C.c_float),
                 ('localization_weight', C.c_float), ('xy_scale', C.c_float), ('wh_scale', C.c_float), ('eps', C.c_float),
                 ('smooth_l1_beta', C.c_float), ('ce_label_smoothing', C.c_float), ('class_weight', C.c_void_p)]
+
+    def __new__(cls, *args, **kwargs):
+        return super().__new__(_LossParams125 if cls is LossParams else cls)
+
+
+class _LossParams125(LossParams):
+    """ssdk_loss_params as of ABI 125: ``quality_from_iou`` behind the older fields (the fifteenth positional argument)."""
+    _fields_ = [('quality_from_iou', C.c_int)]
 
 
 class ConvDesc(C.Structure):

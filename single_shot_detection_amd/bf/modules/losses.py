@@ -13,6 +13,9 @@ the plain sums instead of MultiboxLoss's division by the positives.  Limits, eac
 ``ignore_index`` mapped onto the kernel's -1.  GeneralizedIoULoss (losses.py:109-114) is 1 - box_utils.generalized_iou on
 csrc/boxes.hip, forward only (no autograd: MultiboxLoss's GIoU term has its backward inside the fused kernel).
 
+QualityFocalLoss and VarifocalLoss are not in the reference: the IoU-aware sigmoid losses that train on every anchor (sampler
+``valid_sampler``), on the dense kernels of csrc/loss.hip; same surface, same limits.
+
 torch's own loss classes are re-exported as the reference does (``from torch.nn.modules.loss import *``).  MultiboxLoss puts these of them
 on the fused kernels: CrossEntropyLoss (``label_smoothing``, ``weight``), SmoothL1Loss (``beta``, 0 included), L1Loss, MSELoss and
 HuberLoss (``delta``); any other it refuses with NotImplementedError.
@@ -27,6 +30,8 @@ SSDK_CLS_SIGMOID_FOCAL = 1
 SSDK_CLS_SOFTMAX_FOCAL = 2
 SSDK_CLS_CE_SOFT = 3
 SSDK_CLS_BCE_SOFT = 4
+SSDK_CLS_QUALITY_FOCAL = 5
+SSDK_CLS_VARIFOCAL = 6
 
 
 class _SliceLossFn(torch.autograd.Function):
@@ -45,7 +50,8 @@ class _SliceLossFn(torch.autograd.Function):
         target[0, :, 5] = score_col
         locs = torch.zeros((1, P * 4), dtype=torch.float32, device=dev)
         anchors = torch.ones((P, 4), dtype=torch.float32, device=dev)   # (box term: weight 0, and finite: log(0 / 1 + eps) with eps = 1)
-        sampled = torch.ones((1, P), dtype=torch.uint8, device=dev)
+        # (the IoU-aware kinds: no mask -- every row's class is >= 0 here, and NULL means "every row that is not ignored")
+        sampled = None if kind in (SSDK_CLS_QUALITY_FOCAL, SSDK_CLS_VARIFOCAL) else torch.ones((1, P), dtype=torch.uint8, device=dev)
         ws = _sampler.loss_workspace(1, P, C, dev)
         params = _lib.LossParams(kind, 0, float(gamma), float(alpha), 2, float(epsilon), 1.0, 0.0, 10.0, 5.0, 1.0, 1.0)
         out3 = torch.empty((3,), dtype=torch.float32, device=dev)
@@ -114,6 +120,54 @@ class SigmoidFocalLoss(_Loss):
         col, val = self._one_entry_rows(target, 'SigmoidFocalLoss')
         total = _SliceLossFn.apply(prediction, (col + 1).float(), val, SSDK_CLS_SIGMOID_FOCAL, self.gamma, self.alpha, 0.0)
         return total / prediction.shape[0] if self.reduction == 'mean' else total   # (:52 sums a row's classes, _reduce means over the rows)
+
+
+class _QualityLoss(_Loss):
+    """The IoU-aware sigmoid losses (not in the reference; csrc/loss.hip's dense kernels).  Inside MultiboxLoss a positive's class column
+    is asked for y = mixup weight * q, q = the IoU of the anchor's own decoded box with its ground-truth box (``use_iou``; q = 1 without),
+    every other column and every negative row for 0, and q is a constant of the step.  On their own, ``forward(prediction, target)`` takes
+    the dense target -- at most one non-zero entry per row, whose value is y."""
+    MULTICLASS = True
+    KIND = None
+
+    def _slice(self, prediction, target, gamma, alpha):
+        self._check(prediction)
+        col, val = self._one_entry_rows(target, type(self).__name__)
+        total = _SliceLossFn.apply(prediction, (col + 1).float(), val, self.KIND, gamma, alpha, 0.0)
+        return total / prediction.shape[0] if self.reduction == 'mean' else total   # (like SigmoidFocalLoss: the mean is over the rows)
+
+
+class QualityFocalLoss(_QualityLoss):
+    """Quality Focal Loss (arXiv:2006.04388): |y - s|^beta * bce(x, y), s = sigmoid(x)."""
+    KIND = SSDK_CLS_QUALITY_FOCAL
+
+    def __init__(self, beta=2.0, use_iou=True, reduction='mean'):   # (reduction by name, no **kwargs: MultiboxLoss's 'sum' survives filter_kwargs)
+        super(QualityFocalLoss, self).__init__(reduction=reduction)
+        if not beta >= 1.0:
+            raise ValueError(f'QualityFocalLoss: beta={beta} must be >= 1')
+        self.beta = beta
+        self.use_iou = bool(use_iou)
+
+    def forward(self, prediction, target):
+        return self._slice(prediction, target, self.beta, 0.0)
+
+
+class VarifocalLoss(_QualityLoss):
+    """Varifocal Loss (arXiv:2008.13367): y * bce(x, y) where y > 0, alpha * s^gamma * bce(x, 0) where y == 0."""
+    KIND = SSDK_CLS_VARIFOCAL
+
+    def __init__(self, alpha=0.75, gamma=2.0, use_iou=True, reduction='mean'):
+        super(VarifocalLoss, self).__init__(reduction=reduction)
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f'VarifocalLoss: alpha={alpha} outside [0, 1]')
+        if not gamma >= 0.0:
+            raise ValueError(f'VarifocalLoss: gamma={gamma} must be >= 0')
+        self.alpha = alpha
+        self.gamma = gamma
+        self.use_iou = bool(use_iou)
+
+    def forward(self, prediction, target):
+        return self._slice(prediction, target, self.gamma, self.alpha)
 
 
 class SoftmaxFocalLoss(_Loss):

@@ -17,7 +17,11 @@
 //                      rows only (a gather of x[class] when the log-sum-exp is already there; otherwise the wave
 //                      cooperates on each sampled row).  Partial sums per workgroup, fixed-order final reduce.
 //   loss_bwd_kernel    64-row output tiles: zero-fill, fill the sampled rows, one coalesced write.
+//   loss_dense_fwd_kernel / loss_dense_bwd_kernel   the losses that see EVERY anchor (Quality Focal, Varifocal; SigmoidFocalLoss without
+//                      a mask): 256-row tiles, one thread per row for the box term and the quality, then all threads on the tile's
+//                      contiguous logits with 16-byte accesses; partial sums through the same arrays and loss_finalize_kernel.
 #include <algorithm>
+#include <float.h>
 #include <limits.h>
 #include <math.h>
 
@@ -313,11 +317,12 @@ __global__ void __launch_bounds__(1024) hnm_select_kernel(const float* __restric
     }
 }
 
+// valid != 0: every row that is not ignored (ssdk_valid_sampler), else the positives (sampler.py:10)
 __global__ void __launch_bounds__(256) naive_sampler_kernel(const float* __restrict__ target_cls, int cls_stride, long long n_rows,
-                                                            uint8_t* __restrict__ sampled) {
+                                                            uint8_t* __restrict__ sampled, int valid) {
     for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < n_rows; r += (long long)gridDim.x * blockDim.x) {
         const float cls = target_cls[r * cls_stride];
-        sampled[r] = cls != 0.0f && cls != -1.0f;  // sampler.py:10
+        sampled[r] = (valid || cls != 0.0f) && cls != -1.0f;
     }
 }
 
@@ -368,6 +373,7 @@ struct LossParams {
     float epsilon;  // label smoothing of the soft-target losses (losses.py:13-18)
     float ls;        // CEX kernels: CrossEntropyLoss label_smoothing
     const float* cw; // CEX kernels: CrossEntropyLoss weight [C] or nullptr
+    int quality_from_iou;  // dense kernels: the quality q is the IoU of the decoded prediction (else 1)
 };
 
 // CrossEntropyLoss weight of class c (1 without weights; 0 for a label outside [0, C), which must not read past the [C] array)
@@ -602,7 +608,8 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(const float* __restr
         const int npos = n0, nrows = n1, nposrows = n2;
         // reduce_mean == 2: the plain sums, not divided by the positives (the standalone modules of bf/modules/losses.py)
         const float divider = reduce_mean == 2 ? 1.0f : (float)(npos < 1 ? 1 : npos);  // multibox_loss.py:88
-        const bool focal = cls_kind == SSDK_CLS_SIGMOID_FOCAL || cls_kind == SSDK_CLS_SOFTMAX_FOCAL;
+        const bool focal = cls_kind == SSDK_CLS_SIGMOID_FOCAL || cls_kind == SSDK_CLS_SOFTMAX_FOCAL || cls_kind == SSDK_CLS_QUALITY_FOCAL ||
+                           cls_kind == SSDK_CLS_VARIFOCAL;
         const float mean_div = (focal && reduce_mean == 1) ? (float)nrows : 1.0f;
         float scale = 1.0f;
         if (cls_kind == SSDK_CLS_CE_SOFT) scale = 1.0f / ((float)t / (float)nrows);       // losses.py:89 target.sum(-1).mean() ** -1
@@ -739,6 +746,257 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
     }
 }
 
+// ---- dense sigmoid-target kernels -----------------------------------------------------------------------------------------
+// SSDK_CLS_QUALITY_FOCAL and SSDK_CLS_VARIFOCAL always, SSDK_CLS_SIGMOID_FOCAL when there is no mask (sampled == NULL: every row that is
+// not ignored).  These losses see every anchor, so the work is the [rows, C] logits themselves, not a few sampled rows: tiles of 256
+// rows, a ROW phase (one thread per row: what loss_fwd_kernel / loss_bwd_kernel do per row, plus the quality q) that leaves the row's
+// positive column and target value in LDS, then an ELEMENT phase in which all threads stream the tile's contiguous rows * C logits with
+// 16-byte accesses.  No atomics, nothing zero-filled beforehand, sums in an order fixed by the launch.
+
+constexpr int kDenseRows = kLossThreads;   // rows of a tile: one per thread in the row phase (256 rows * C floats start 16-byte aligned)
+constexpr int kRowOff = INT_MIN;           // positive-column marker: the row is not sampled (contributes nothing)
+constexpr int kRowNoPositive = -1;         // ... sampled, every target 0
+
+// b^g for b >= 0, g >= 0 (the default exponents are multiplies; 0^0 = 1)
+__device__ __forceinline__ float pow_small(float b, float g) {
+    if (g == 2.0f) return b * b;
+    if (g == 1.0f) return b;
+    if (g == 0.0f) return 1.0f;
+    return __powf(b, g);
+}
+
+// the quality of a positive (include/ssdk.h): plain IoU of predicted corners P against target corners T, in [0, 1], 0 when undefined
+__device__ __forceinline__ float box_quality(float4 P, float4 T) {
+    const float inter = area4(tmaxf(P.x, T.x), tmaxf(P.y, T.y), tminf(P.z, T.z), tminf(P.w, T.w));
+    const float uni = area4(P.x, P.y, P.z, P.w) + area4(T.x, T.y, T.z, T.w) - inter;
+    const float q = inter / uni;
+    if (!(uni > 0.0f) || !(fabsf(q) <= FLT_MAX)) return 0.0f;
+    return fminf(fmaxf(q, 0.0f), 1.0f);
+}
+
+// one element of the sigmoid-target kinds, target y: the value, or (GRAD) d value / dx  (include/ssdk.h)
+template <bool GRAD>
+__device__ __forceinline__ float dense_elem(const LossParams& p, float x, float y) {
+    if (p.cls_kind == SSDK_CLS_SIGMOID_FOCAL) return GRAD ? focal_elem_grad(x, y, p.gamma, p.alpha) : focal_elem(x, y, p.gamma, p.alpha);
+    const float e = __expf(-fabsf(x)), inv = 1.0f / (1.0f + e);
+    const float s = x >= 0.0f ? inv : e * inv, oms = x >= 0.0f ? e * inv : inv;   // sigmoid(x), 1 - sigmoid(x)
+    const float bce = fmaxf(x, 0.0f) - x * y + log1pf(e);
+    if (p.cls_kind == SSDK_CLS_QUALITY_FOCAL) {
+        const float d = s - y, ad = fabsf(d), w = pow_small(ad, p.gamma);
+        if (!GRAD) return w * bce;
+        const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+        return p.gamma * pow_small(ad, p.gamma - 1.0f) * sg * s * oms * bce + w * d;
+    }
+    if (y > 0.0f) return GRAD ? y * (s - y) : y * bce;   // SSDK_CLS_VARIFOCAL
+    const float w = p.alpha * pow_small(s, p.gamma);
+    return GRAD ? w * (p.gamma * oms * bce + s) : w * bce;
+}
+
+// where element 4 * threadIdx.x of a tile sits (row, column), and how far 4 * kLossThreads elements move it: the element phase derives
+// every element's row from these by additions (two integer divisions per thread and launch, none per element)
+struct DenseWalk {
+    int row0, col0, step_row, step_col;
+    __device__ __forceinline__ explicit DenseWalk(int C)
+        : row0(4 * (int)threadIdx.x / C), col0(4 * (int)threadIdx.x % C), step_row(4 * kLossThreads / C), step_col(4 * kLossThreads % C) {}
+};
+
+template <int LK>
+__global__ void __launch_bounds__(kLossThreads) loss_dense_fwd_kernel(LossParams p, const float* __restrict__ scores,
+                                                                      const float4* __restrict__ locs, const float4* __restrict__ anchors,
+                                                                      float* __restrict__ target, const uint8_t* __restrict__ sampled,
+                                                                      long long n_rows, int A, float* __restrict__ quality,
+                                                                      float* __restrict__ partials, int* __restrict__ counts) {
+    __shared__ float s_red[kLossThreads / kWave];
+    __shared__ int s_redi[kLossThreads / kWave];
+    __shared__ int s_col[kDenseRows + 1];    // (+1: the walk steps onto the row after the tile's last element, and reads it)
+    __shared__ float s_y[kDenseRows + 1];
+    float cls_acc = 0.0f, loc_acc = 0.0f;
+    int npos = 0, nrows = 0;
+    const int tid = threadIdx.x, C = p.C;
+    const DenseWalk walk(C);
+    if (tid == 0) { s_col[kDenseRows] = kRowOff; s_y[kDenseRows] = 0.0f; }
+    const long long n_tiles = (n_rows + kDenseRows - 1) / kDenseRows;
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long r0 = tile * kDenseRows;
+        const int rows = (int)min((long long)kDenseRows, n_rows - r0);
+        // ---- row phase
+        int colm = kRowOff;
+        float y = 0.0f;
+        if (tid < rows) {
+            const long long r = r0 + tid;
+            float2* trow = reinterpret_cast<float2*>(target + r * 6);  // 24-byte rows: 8-byte aligned
+            float2 t01 = trow[0], t23 = trow[1];
+            const float2 t45 = trow[2];
+            const int cls = (int)t45.x;  // multibox_loss.py:48 .long()
+            const bool pos = cls != 0 && cls != -1;
+            const bool smp = sampled ? sampled[r] != 0 : cls != -1;
+            npos += pos;
+            nrows += smp;
+            const float4 pr = anchors[r % A];
+            float q = 1.0f;
+            float4 l = make_float4(0.f, 0.f, 0.f, 0.f), P = l;
+            if (pos) l = locs[r];
+            if (pos && (LK == SSDK_LOC_GIOU || p.quality_from_iou)) {
+                float4 cen;
+                P = decode_corners(l, pr, p.xy_scale, p.wh_scale, cen);
+            }
+            if (pos && p.quality_from_iou) q = box_quality(P, make_float4(t01.x, t01.y, t23.x, t23.y));   // the RAW corners: before the encode
+            quality[r] = q;
+            if constexpr (LK == SSDK_LOC_GIOU) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
+                if (pos) loc_acc += giou_loss(P, make_float4(t01.x, t01.y, t23.x, t23.y));
+            } else {
+                // box_utils.py:33-34 to_centroids(inplace), then box_coder.py:22-30 encode_box(inplace) -- op for op loss_fwd_kernel's
+                t23.x -= t01.x; t23.y -= t01.y;
+                t01.x += t23.x / 2.0f; t01.y += t23.y / 2.0f;
+                t01.x -= pr.x; t01.y -= pr.y;
+                t01.x /= pr.z; t01.y /= pr.w;
+                t01.x *= p.xy_scale; t01.y *= p.xy_scale;
+                t23.x /= pr.z; t23.y /= pr.w;
+                t23.x += p.eps; t23.y += p.eps;
+                t23.x = logf(t23.x); t23.y = logf(t23.y);
+                t23.x *= p.wh_scale; t23.y *= p.wh_scale;
+                trow[0] = t01; trow[1] = t23;
+                if (pos)  // multibox_loss.py:84-86
+                    loc_acc += box_loss<LK>(l.x, t01.x, p.beta) + box_loss<LK>(l.y, t01.y, p.beta) + box_loss<LK>(l.z, t23.x, p.beta) +
+                               box_loss<LK>(l.w, t23.y, p.beta);
+            }
+            if (smp) {
+                colm = (pos && cls >= 1) ? cls - 1 : kRowNoPositive;   // multibox_loss.py:64-67
+                y = pos ? t45.y * q : 0.0f;
+            }
+        }
+        __syncthreads();   // (the previous tile's element phase has read its rows)
+        s_col[tid] = colm;
+        s_y[tid] = y;
+        if (!__syncthreads_or(colm != kRowOff)) continue;   // under a mask: a tile without a sampled row reads no scores
+        // ---- element phase
+        const int nfloat = rows * C;
+        const float* src = scores + r0 * C;   // 16-byte aligned: r0 * C * 4 = tile * 1024 * C
+        int rr = walk.row0, cc = walk.col0;
+        for (int v = tid; v < (nfloat >> 2); v += kLossThreads) {
+            const float4 x4 = reinterpret_cast<const float4*>(src)[v];
+            const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
+            int r_ = rr, c_ = cc, pc = s_col[r_];
+            float py = s_y[r_];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (pc != kRowOff) cls_acc += dense_elem<false>(p, xs[j], c_ == pc ? py : 0.0f);
+                if (++c_ == C) { c_ = 0; ++r_; pc = s_col[r_]; py = s_y[r_]; }
+            }
+            cc += walk.step_col; rr += walk.step_row;
+            if (cc >= C) { cc -= C; ++rr; }
+        }
+        if (tid < (nfloat & 3)) {   // (only the last, partial tile has a tail)
+            const int e = (nfloat & ~3) + tid, r_ = e / C, c_ = e - r_ * C, pc = s_col[r_];
+            if (pc != kRowOff) cls_acc += dense_elem<false>(p, src[e], c_ == pc ? s_y[r_] : 0.0f);
+        }
+    }
+    const float cs_ = block_sum(cls_acc, s_red);
+    const float ls_ = block_sum(loc_acc, s_red);
+    const int np_ = block_sum(npos, s_redi);
+    const int nr_ = block_sum(nrows, s_redi);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = cs_;
+        partials[kMaxPartials + blockIdx.x] = ls_;
+        partials[2 * kMaxPartials + blockIdx.x] = 0.0f;
+        counts[blockIdx.x] = np_;
+        counts[kMaxPartials + blockIdx.x] = nr_;
+        counts[2 * kMaxPartials + blockIdx.x] = 0;
+    }
+}
+
+template <int LK>
+__global__ void __launch_bounds__(kLossThreads) loss_dense_bwd_kernel(LossParams p, int reduce_mean, float cls_w, float loc_w,
+                                                                      const float* __restrict__ scores, const float4* __restrict__ locs,
+                                                                      const float4* __restrict__ anchors, int A,
+                                                                      const float* __restrict__ target, const uint8_t* __restrict__ sampled,
+                                                                      const float* __restrict__ grad_out, long long n_rows,
+                                                                      const float* __restrict__ quality, const LossState* __restrict__ state,
+                                                                      float* __restrict__ dscores, float4* __restrict__ dlocs,
+                                                                      unsigned char* __restrict__ row_mask, int grad_single) {
+    __shared__ int s_col[kDenseRows + 1];
+    __shared__ float s_y[kDenseRows + 1];
+    const float divider = state->divider;
+    const float g_cls = grad_out[0] * state->scale * cls_w / divider / (reduce_mean ? state->mean_div : 1.0f);
+    const float g_loc = grad_out[grad_single ? 0 : 1] * loc_w / divider;
+    const int tid = threadIdx.x, C = p.C;
+    const DenseWalk walk(C);
+    if (tid == 0) { s_col[kDenseRows] = kRowOff; s_y[kDenseRows] = 0.0f; }
+    const long long n_tiles = (n_rows + kDenseRows - 1) / kDenseRows;
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long r0 = tile * kDenseRows;
+        const int rows = (int)min((long long)kDenseRows, n_rows - r0);
+        // ---- row phase
+        int colm = kRowOff;
+        float y = 0.0f;
+        if (tid < rows) {
+            const long long r = r0 + tid;
+            const float2* trow = reinterpret_cast<const float2*>(target + r * 6);
+            const float2 t01 = trow[0], t23 = trow[1], t45 = trow[2];
+            const int cls = (int)t45.x;
+            const bool pos = cls != 0 && cls != -1;
+            const bool smp = sampled ? sampled[r] != 0 : cls != -1;
+            if (smp) {
+                colm = (pos && cls >= 1) ? cls - 1 : kRowNoPositive;
+                y = pos ? t45.y * quality[r] : 0.0f;   // the forward's q: the SmoothL1 family has overwritten the raw corners
+            }
+            float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (pos) {
+                const float4 l = locs[r];
+                if constexpr (LK == SSDK_LOC_GIOU) {
+                    const float4 pr = anchors[r % A];
+                    float4 cen;
+                    const float4 P = decode_corners(l, pr, p.xy_scale, p.wh_scale, cen);
+                    const float4 d = giou_loss_grad(P, make_float4(t01.x, t01.y, t23.x, t23.y));
+                    // corners = c -+ wh/2 ; c = p_xy + p_wh t / xy_scale ; wh = p_wh exp(t / wh_scale)
+                    g = make_float4((d.x + d.z) * pr.z / p.xy_scale * g_loc, (d.y + d.w) * pr.w / p.xy_scale * g_loc,
+                                    (d.z - d.x) * 0.5f * cen.z / p.wh_scale * g_loc, (d.w - d.y) * 0.5f * cen.w / p.wh_scale * g_loc);
+                } else {
+                    g = make_float4(box_loss_grad<LK>(l.x, t01.x, p.beta) * g_loc, box_loss_grad<LK>(l.y, t01.y, p.beta) * g_loc,
+                                    box_loss_grad<LK>(l.z, t23.x, p.beta) * g_loc, box_loss_grad<LK>(l.w, t23.y, p.beta) * g_loc);
+                }
+            }
+            dlocs[r] = g;
+            // anchors whose gradient rows can be non-zero (a classification term, or a box term): what ssdk_heads_bwd_ex may rely on
+            if (row_mask) row_mask[r] = (smp || pos) ? 1 : 0;
+        }
+        __syncthreads();   // (the previous tile's element phase has read its rows)
+        s_col[tid] = colm;
+        s_y[tid] = y;
+        const bool any = __syncthreads_or(colm != kRowOff);
+        // ---- element phase: dscores straight from registers
+        const int nfloat = rows * C;
+        const float* src = scores + r0 * C;   // 16-byte aligned: r0 * C * 4 = tile * 1024 * C
+        float* dst = dscores + r0 * C;
+        if (!any) {   // under a mask: a tile without a sampled row is zeros, and reads no scores
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int v = tid; v < (nfloat >> 2); v += kLossThreads) reinterpret_cast<float4*>(dst)[v] = z;
+            if (tid < (nfloat & 3)) dst[(nfloat & ~3) + tid] = 0.0f;
+            continue;
+        }
+        int rr = walk.row0, cc = walk.col0;
+        for (int v = tid; v < (nfloat >> 2); v += kLossThreads) {
+            const float4 x4 = reinterpret_cast<const float4*>(src)[v];
+            const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
+            float gs[4];
+            int r_ = rr, c_ = cc, pc = s_col[r_];
+            float py = s_y[r_];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                gs[j] = pc != kRowOff ? dense_elem<true>(p, xs[j], c_ == pc ? py : 0.0f) * g_cls : 0.0f;
+                if (++c_ == C) { c_ = 0; ++r_; pc = s_col[r_]; py = s_y[r_]; }
+            }
+            reinterpret_cast<float4*>(dst)[v] = make_float4(gs[0], gs[1], gs[2], gs[3]);
+            cc += walk.step_col; rr += walk.step_row;
+            if (cc >= C) { cc -= C; ++rr; }
+        }
+        if (tid < (nfloat & 3)) {   // (only the last, partial tile has a tail)
+            const int e = (nfloat & ~3) + tid, r_ = e / C, c_ = e - r_ * C, pc = s_col[r_];
+            dst[e] = pc != kRowOff ? dense_elem<true>(p, src[e], c_ == pc ? s_y[r_] : 0.0f) * g_cls : 0.0f;
+        }
+    }
+}
+
 // ---- box coder (elementwise) ------------------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(256) encode_box_kernel(const float4* __restrict__ boxes, const float4* __restrict__ priors,
@@ -836,14 +1094,23 @@ extern "C" int ssdk_naive_sampler(const float* target_classes, int class_stride,
                                   void* stream) {
     SSDK_REQUIRE(target_classes && sampled && batch > 0 && num_anchors > 0 && class_stride >= 1, SSDK_E_INVALID, "ssdk_naive_sampler: bad arguments");
     const long long n_rows = (long long)batch * num_anchors;
-    hipLaunchKernelGGL(naive_sampler_kernel, dim3(stream_grid(n_rows, 256)), dim3(256), 0, (hipStream_t)stream, target_classes, class_stride, n_rows, sampled);
+    hipLaunchKernelGGL(naive_sampler_kernel, dim3(stream_grid(n_rows, 256)), dim3(256), 0, (hipStream_t)stream, target_classes, class_stride, n_rows, sampled, 0);
+    SSDK_CHECK_LAUNCH("naive_sampler_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_valid_sampler(const float* target_classes, int class_stride, int batch, int num_anchors, uint8_t* sampled,
+                                  void* stream) {
+    SSDK_REQUIRE(target_classes && sampled && batch > 0 && num_anchors > 0 && class_stride >= 1, SSDK_E_INVALID, "ssdk_valid_sampler: bad arguments");
+    const long long n_rows = (long long)batch * num_anchors;
+    hipLaunchKernelGGL(naive_sampler_kernel, dim3(stream_grid(n_rows, 256)), dim3(256), 0, (hipStream_t)stream, target_classes, class_stride, n_rows, sampled, 1);
     SSDK_CHECK_LAUNCH("naive_sampler_kernel");
     return SSDK_OK;
 }
 
 static int check_loss_params(const char* fn, const ssdk_loss_params* q) {
     SSDK_REQUIRE(q, SSDK_E_INVALID, "%s: null params", fn);
-    SSDK_REQUIRE(q->cls_kind >= SSDK_CLS_CROSS_ENTROPY && q->cls_kind <= SSDK_CLS_BCE_SOFT, SSDK_E_INVALID, "%s: cls_kind=%d", fn, q->cls_kind);
+    SSDK_REQUIRE(q->cls_kind >= SSDK_CLS_CROSS_ENTROPY && q->cls_kind <= SSDK_CLS_VARIFOCAL, SSDK_E_INVALID, "%s: cls_kind=%d", fn, q->cls_kind);
     SSDK_REQUIRE(q->loc_kind >= SSDK_LOC_SMOOTH_L1 && q->loc_kind <= SSDK_LOC_HUBER, SSDK_E_INVALID, "%s: loc_kind=%d", fn, q->loc_kind);
     SSDK_REQUIRE(q->loc_kind != SSDK_LOC_SMOOTH_L1 || q->smooth_l1_beta >= 0, SSDK_E_INVALID, "%s: SmoothL1 beta must be >= 0", fn);
     SSDK_REQUIRE(q->loc_kind != SSDK_LOC_HUBER || q->smooth_l1_beta > 0, SSDK_E_INVALID, "%s: Huber delta must be > 0", fn);
@@ -852,6 +1119,11 @@ static int check_loss_params(const char* fn, const ssdk_loss_params* q) {
                  "%s: ce_label_smoothing / class_weight apply to SSDK_CLS_CROSS_ENTROPY only", fn);
     SSDK_REQUIRE(q->soft_epsilon >= 0.0f && q->soft_epsilon < 1.0f, SSDK_E_INVALID, "%s: epsilon outside [0, 1) (losses.py:15)", fn);
     SSDK_REQUIRE(q->reduce_mean >= 0 && q->reduce_mean <= 2, SSDK_E_INVALID, "%s: reduce_mean=%d (0 sum, 1 mean, 2 sums not divided by the positives)", fn, q->reduce_mean);
+    const bool quality = q->cls_kind == SSDK_CLS_QUALITY_FOCAL || q->cls_kind == SSDK_CLS_VARIFOCAL;
+    SSDK_REQUIRE(quality || q->quality_from_iou == 0, SSDK_E_INVALID, "%s: quality_from_iou applies to SSDK_CLS_QUALITY_FOCAL / _VARIFOCAL only", fn);
+    SSDK_REQUIRE(q->cls_kind != SSDK_CLS_QUALITY_FOCAL || q->focal_gamma >= 1.0f, SSDK_E_INVALID, "%s: Quality Focal Loss beta (focal_gamma) must be >= 1", fn);
+    SSDK_REQUIRE(q->cls_kind != SSDK_CLS_VARIFOCAL || (q->focal_gamma >= 0.0f && q->focal_alpha >= 0.0f && q->focal_alpha <= 1.0f), SSDK_E_INVALID,
+                 "%s: Varifocal Loss needs gamma >= 0 and alpha in [0, 1]", fn);
     return SSDK_OK;
 }
 
@@ -862,6 +1134,7 @@ static LossParams to_device_params(const ssdk_loss_params* q, int C, int lse_val
     p.beta = q->smooth_l1_beta; p.loc_kind = q->loc_kind; p.epsilon = q->soft_epsilon;
     if (p.loc_kind == SSDK_LOC_SMOOTH_L1 && p.beta == 0.0f) p.loc_kind = SSDK_LOC_L1;   // torch smooth_l1_loss: beta == 0 is l1_loss
     p.ls = q->ce_label_smoothing; p.cw = q->class_weight;   // (check_loss_params: 0 / NULL unless SSDK_CLS_CROSS_ENTROPY)
+    p.quality_from_iou = q->quality_from_iou;
     return p;
 }
 
@@ -883,6 +1156,25 @@ static LossBwdFn bwd_kernel_for(const LossParams& p) {
         {loss_bwd_kernel<0, true>, loss_bwd_kernel<1, true>, loss_bwd_kernel<2, true>, loss_bwd_kernel<3, true>, loss_bwd_kernel<4, true>}};
     return k[ce_extended(p)][p.loc_kind];
 }
+using DenseFwdFn = decltype(&loss_dense_fwd_kernel<SSDK_LOC_SMOOTH_L1>);
+using DenseBwdFn = decltype(&loss_dense_bwd_kernel<SSDK_LOC_SMOOTH_L1>);
+static DenseFwdFn dense_fwd_kernel_for(const LossParams& p) {
+    static const DenseFwdFn k[5] = {loss_dense_fwd_kernel<0>, loss_dense_fwd_kernel<1>, loss_dense_fwd_kernel<2>, loss_dense_fwd_kernel<3>, loss_dense_fwd_kernel<4>};
+    return k[p.loc_kind];
+}
+static DenseBwdFn dense_bwd_kernel_for(const LossParams& p) {
+    static const DenseBwdFn k[5] = {loss_dense_bwd_kernel<0>, loss_dense_bwd_kernel<1>, loss_dense_bwd_kernel<2>, loss_dense_bwd_kernel<3>, loss_dense_bwd_kernel<4>};
+    return k[p.loc_kind];
+}
+// The dense kernels' kinds: the two IoU-aware ones always, SigmoidFocalLoss only without a mask (with one it keeps the kernels it had).
+static bool dense_path(int cls_kind, const uint8_t* sampled) {
+    return cls_kind == SSDK_CLS_QUALITY_FOCAL || cls_kind == SSDK_CLS_VARIFOCAL || (cls_kind == SSDK_CLS_SIGMOID_FOCAL && !sampled);
+}
+// Workgroups of a dense kernel: the tiles, at most what the device holds at once (they stride over the rest) and at most kMaxPartials.
+static int dense_grid(const void* fn, long long n_rows) {
+    const long long n_tiles = (n_rows + kDenseRows - 1) / kDenseRows;
+    return (int)std::min<long long>(n_tiles, std::min(resident_blocks(fn, 0), kMaxPartials));
+}
 
 extern "C" int ssdk_multibox_loss_fwd(const ssdk_loss_params* params, const float* scores, const float* locs, const float* anchors,
                                       float* target, const uint8_t* sampled, int batch, int num_anchors, int num_classes, int lse_valid,
@@ -891,17 +1183,28 @@ extern "C" int ssdk_multibox_loss_fwd(const ssdk_loss_params* params, const floa
     if (rc) return rc;
     rc = check_loss_params("ssdk_multibox_loss_fwd", params);
     if (rc) return rc;
-    SSDK_REQUIRE(locs && anchors && target && sampled && out3, SSDK_E_INVALID, "ssdk_multibox_loss_fwd: null pointer");
+    SSDK_REQUIRE(locs && anchors && target && out3, SSDK_E_INVALID, "ssdk_multibox_loss_fwd: null pointer");
+    const bool dense = dense_path(params->cls_kind, sampled);
+    SSDK_REQUIRE(sampled || dense, SSDK_E_INVALID, "ssdk_multibox_loss_fwd: sampled == NULL needs SSDK_CLS_SIGMOID_FOCAL, _QUALITY_FOCAL or _VARIFOCAL");
     SSDK_REQUIRE(((uintptr_t)locs & 15) == 0 && ((uintptr_t)anchors & 15) == 0 && ((uintptr_t)target & 7) == 0, SSDK_E_INVALID,
                  "ssdk_multibox_loss_fwd: locs/anchors need 16-byte and target 8-byte alignment");
     hipStream_t s = (hipStream_t)stream;
     const long long n_rows = (long long)batch * num_anchors;
     LossWs w = carve_loss_ws(workspace, (size_t)n_rows, nullptr);
     LossParams p = to_device_params(params, num_classes, lse_valid);
-    const int grid = stream_grid(n_rows, kLossThreads);
-    hipLaunchKernelGGL(fwd_kernel_for(p), dim3(grid), dim3(kLossThreads), 0, s, p, scores, (const float4*)locs, (const float4*)anchors,
-                       target, sampled, n_rows, num_anchors, w.lse, w.partials, w.counts);
-    SSDK_CHECK_LAUNCH("loss_fwd_kernel");
+    int grid;
+    if (dense) {
+        const DenseFwdFn fwd = dense_fwd_kernel_for(p);
+        grid = dense_grid((const void*)fwd, n_rows);
+        hipLaunchKernelGGL(fwd, dim3(grid), dim3(kLossThreads), 0, s, p, scores, (const float4*)locs, (const float4*)anchors, target, sampled,
+                           n_rows, num_anchors, w.lse, w.partials, w.counts);
+        SSDK_CHECK_LAUNCH("loss_dense_fwd_kernel");
+    } else {
+        grid = stream_grid(n_rows, kLossThreads);
+        hipLaunchKernelGGL(fwd_kernel_for(p), dim3(grid), dim3(kLossThreads), 0, s, p, scores, (const float4*)locs, (const float4*)anchors,
+                           target, sampled, n_rows, num_anchors, w.lse, w.partials, w.counts);
+        SSDK_CHECK_LAUNCH("loss_fwd_kernel");
+    }
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, w.partials, grid, w.counts, params->cls_kind, params->reduce_mean,
                        params->classification_weight, params->localization_weight, w.state, out3);
     SSDK_CHECK_LAUNCH("loss_finalize_kernel");
@@ -923,18 +1226,28 @@ extern "C" int ssdk_multibox_loss_bwd_ex(const ssdk_loss_params* params, const f
     if (rc) return rc;
     rc = check_loss_params("ssdk_multibox_loss_bwd", params);
     if (rc) return rc;
-    SSDK_REQUIRE(locs && anchors && target && sampled && grad_out && dscores && dlocs, SSDK_E_INVALID, "ssdk_multibox_loss_bwd: null pointer");
+    SSDK_REQUIRE(locs && anchors && target && grad_out && dscores && dlocs, SSDK_E_INVALID, "ssdk_multibox_loss_bwd: null pointer");
+    const bool dense = dense_path(params->cls_kind, sampled);
+    SSDK_REQUIRE(sampled || dense, SSDK_E_INVALID, "ssdk_multibox_loss_bwd: sampled == NULL needs SSDK_CLS_SIGMOID_FOCAL, _QUALITY_FOCAL or _VARIFOCAL");
     SSDK_REQUIRE(((uintptr_t)dscores & 15) == 0 && ((uintptr_t)dlocs & 15) == 0 && ((uintptr_t)locs & 15) == 0 && ((uintptr_t)anchors & 15) == 0,
                  SSDK_E_INVALID, "ssdk_multibox_loss_bwd: dscores/dlocs/locs/anchors must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const long long n_rows = (long long)batch * num_anchors;
     LossWs w = carve_loss_ws(workspace, (size_t)n_rows, nullptr);
     LossParams p = to_device_params(params, num_classes, 1);
+    const bool focal = params->cls_kind == SSDK_CLS_SIGMOID_FOCAL || params->cls_kind == SSDK_CLS_SOFTMAX_FOCAL || dense;
+    if (dense) {
+        const DenseBwdFn bwd = dense_bwd_kernel_for(p);
+        hipLaunchKernelGGL(bwd, dim3(dense_grid((const void*)bwd, n_rows)), dim3(kLossThreads), 0, s, p, focal ? params->reduce_mean : 0,
+                           params->classification_weight, params->localization_weight, scores, (const float4*)locs, (const float4*)anchors,
+                           num_anchors, target, sampled, grad_out, n_rows, w.lse, w.state, dscores, (float4*)dlocs, row_mask, grad_single ? 1 : 0);
+        SSDK_CHECK_LAUNCH("loss_dense_bwd_kernel");
+        return SSDK_OK;
+    }
     const LossBwdFn bwd = bwd_kernel_for(p);
     const size_t lds = (size_t)kTileRows * num_classes * sizeof(float);
     if (lds > 48 * 1024)
         SSDK_CHECK_HIP(hipFuncSetAttribute((const void*)bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const bool focal = params->cls_kind == SSDK_CLS_SIGMOID_FOCAL || params->cls_kind == SSDK_CLS_SOFTMAX_FOCAL;
     hipLaunchKernelGGL(bwd, dim3((unsigned)std::min<long long>((n_rows + kTileRows - 1) / kTileRows, 1 << 20)), dim3(kLossThreads), lds, s, p, focal ? params->reduce_mean : 0,
                        params->classification_weight, params->localization_weight, scores, (const float4*)locs, (const float4*)anchors,
                        num_anchors, target, sampled, grad_out, n_rows, w.lse, w.state, dscores, (float4*)dlocs, row_mask, grad_single ? 1 : 0);

@@ -16,6 +16,10 @@ SSDK_CLS_SIGMOID_FOCAL = 1
 SSDK_CLS_SOFTMAX_FOCAL = 2
 SSDK_CLS_CE_SOFT = 3
 SSDK_CLS_BCE_SOFT = 4
+SSDK_CLS_QUALITY_FOCAL = 5
+SSDK_CLS_VARIFOCAL = 6
+# the sigmoid-target kinds: for these "every anchor that is not ignored" needs no mask (sampled = NULL: the dense kernels of csrc/loss.hip)
+_NULL_MASK_KINDS = (SSDK_CLS_SIGMOID_FOCAL, SSDK_CLS_QUALITY_FOCAL, SSDK_CLS_VARIFOCAL)
 SSDK_LOC_SMOOTH_L1 = 0
 SSDK_LOC_GIOU = 1
 SSDK_LOC_L1 = 2
@@ -50,6 +54,7 @@ class _MultiboxLossFn(torch.autograd.Function):
         cls_col = target[..., CLASS_INDEX]
         fn, kw = _unwrap_sampler(module.sampler)
         lse_valid = 0
+        null_mask = False
         if fn is _sampler.hard_negative_mining and {'negative_per_positive_ratio', 'min_negative_per_image'} <= set(kw):
             mask = torch.empty((B, A), dtype=torch.uint8, device=dev)
             _lib.check(lib.ssdk_hard_negative_mining(_lib.ptr(scores), cls_col.data_ptr(), 6, B, A, C,
@@ -61,16 +66,23 @@ class _MultiboxLossFn(torch.autograd.Function):
             mask = torch.empty((B, A), dtype=torch.uint8, device=dev)
             _lib.check(lib.ssdk_naive_sampler(cls_col.data_ptr(), 6, B, A, _lib.ptr(mask), _lib.current_stream()),
                        'ssdk_naive_sampler')
+        elif fn is _sampler.valid_sampler:
+            # the mask is this function's output (last_sampled_mask) only: the sigmoid-target kinds read the class column instead
+            mask = torch.empty((B, A), dtype=torch.uint8, device=dev)
+            _lib.check(lib.ssdk_valid_sampler(cls_col.data_ptr(), 6, B, A, _lib.ptr(mask), _lib.current_stream()),
+                       'ssdk_valid_sampler')
+            null_mask = module.cls_kind in _NULL_MASK_KINDS
         else:  # any user sampler with the reference's signature (multibox_loss.py:58)
             mask = module.sampler(scores.view(B, A, C), cls_col.long()).to(torch.uint8).contiguous()
         out3 = torch.empty((3,), dtype=torch.float32, device=dev)
         params = module.loss_params(dev, C)
         _lib.check(lib.ssdk_multibox_loss_fwd(ctypes.byref(params), _lib.ptr(scores), _lib.ptr(locs), _lib.ptr(anchors),
-                                              _lib.ptr(target), _lib.ptr(mask), B, A, C, lse_valid, _lib.ptr(out3), _lib.ptr(ws),
+                                              _lib.ptr(target), None if null_mask else _lib.ptr(mask), B, A, C, lse_valid, _lib.ptr(out3), _lib.ptr(ws),
                                               ws.numel(), _lib.current_stream()), 'ssdk_multibox_loss_fwd')
         ctx.save_for_backward(scores, locs, anchors, target, mask, ws)
         ctx.module = module
         ctx.shape = (B, A, C)
+        ctx.null_mask = null_mask
         ctx.sparse_rows = fn is _sampler.hard_negative_mining or fn is _sampler.naive_sampler   # (the gradient rows of the anchors that were not sampled are zeros)
         ctx.mark_non_differentiable(mask)
         ctx.set_materialize_grads(False)   # (an output nobody differentiated arrives as None, not as a zero tensor made by a fill launch)
@@ -100,7 +112,8 @@ class _MultiboxLossFn(torch.autograd.Function):
         # backward of this pass -- if it receives these very tensors -- reads only those rows instead of scanning all of dscores
         row_mask = torch.empty((B, A), dtype=torch.uint8, device=scores.device) if ctx.sparse_rows and not _NO_ROW_HINT else None
         _lib.check(_lib.lib().ssdk_multibox_loss_bwd_ex(ctypes.byref(params), _lib.ptr(scores), _lib.ptr(locs), _lib.ptr(anchors),
-                                                        _lib.ptr(target), _lib.ptr(mask), _lib.ptr(grad_out), 1 if single else 0, B, A, C, _lib.ptr(dscores),
+                                                        _lib.ptr(target), None if ctx.null_mask else _lib.ptr(mask), _lib.ptr(grad_out), 1 if single else 0, B, A, C,
+                                                        _lib.ptr(dscores),
                                                         _lib.ptr(dlocs), _lib.ptr(row_mask), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
                    'ssdk_multibox_loss_bwd')
         if row_mask is not None:
@@ -136,6 +149,7 @@ class MultiboxLoss(nn.Module):
         cl = self.classification_loss
         self.focal_gamma, self.focal_alpha, self.focal_reduce_mean, self.soft_epsilon = 2.0, 0.25, 0, 0.0
         self.ce_label_smoothing, self.class_weight = 0.0, None
+        self.quality_from_iou = 0
         if isinstance(cl, losses.CrossEntropyLoss):
             if cl.reduction != 'sum' or cl.ignore_index != IGNORE_CLASS:
                 raise NotImplementedError('CrossEntropyLoss: only reduction=sum, ignore_index=-1')
@@ -153,6 +167,15 @@ class MultiboxLoss(nn.Module):
             self.cls_kind = SSDK_CLS_SIGMOID_FOCAL
             self.focal_gamma, self.focal_alpha = float(cl.gamma), float(cl.alpha)
             self.focal_reduce_mean = 1 if cl.reduction == 'mean' else 0
+        elif isinstance(cl, (losses.QualityFocalLoss, losses.VarifocalLoss)):
+            if cl.reduction not in ('mean', 'sum'):
+                raise NotImplementedError(f"{type(cl).__name__}: reduction must be 'mean' or 'sum'")
+            if isinstance(cl, losses.QualityFocalLoss):
+                self.cls_kind, self.focal_gamma = SSDK_CLS_QUALITY_FOCAL, float(cl.beta)
+            else:
+                self.cls_kind, self.focal_gamma, self.focal_alpha = SSDK_CLS_VARIFOCAL, float(cl.gamma), float(cl.alpha)
+            self.focal_reduce_mean = 1 if cl.reduction == 'mean' else 0
+            self.quality_from_iou = 1 if cl.use_iou else 0
         elif isinstance(cl, losses.SoftmaxFocalLoss):
             if cl.reduction not in ('mean', 'sum') or cl.ignore_index != IGNORE_CLASS:
                 raise NotImplementedError("SoftmaxFocalLoss: reduction must be 'mean' or 'sum' and ignore_index -1")
@@ -209,7 +232,7 @@ class MultiboxLoss(nn.Module):
         return _lib.LossParams(self.cls_kind, self.loc_kind, self.focal_gamma, self.focal_alpha, self.focal_reduce_mean,
                                self.soft_epsilon, float(self.classification_weight), float(self.localization_weight),
                                float(self.box_coder.xy_scale), float(self.box_coder.wh_scale), float(self.box_coder.eps),
-                               self.smooth_l1_beta, self.ce_label_smoothing, None if w is None else w.data_ptr())
+                               self.smooth_l1_beta, self.ce_label_smoothing, None if w is None else w.data_ptr(), self.quality_from_iou)
 
     def forward(self, pred, anchors, target):
         """

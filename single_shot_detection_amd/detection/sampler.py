@@ -1,8 +1,8 @@
 """Samplers -- mirror of detection/sampler.py:9-25 on libssdk (csrc/loss.hip).
 
 Signature kept: ``f(predictions [B,A,C], target_classes [B,A]) -> bool [B,A]``.  MultiboxLoss recognises these two
-functions (also wrapped in ``functools.partial``) and runs them fused with the loss; any other callable is simply
-called and its mask handed to the loss kernel.
+functions and ``valid_sampler`` (also wrapped in ``functools.partial``) and runs them fused with the loss; any other
+callable is simply called and its mask handed to the loss kernel.
 """
 import torch
 
@@ -31,6 +31,18 @@ def naive_sampler(predictions, target_classes):
     mask = torch.empty((B, A), dtype=torch.uint8, device=target_classes.device)
     _lib.check(_lib.lib().ssdk_naive_sampler(cls.data_ptr(), stride, B, A, _lib.ptr(mask), _lib.current_stream()),
                'ssdk_naive_sampler')
+    return mask.bool()
+
+
+def valid_sampler(predictions, target_classes):
+    """Every anchor that is not ignored: what the losses that train the classifier on all anchors take (QualityFocalLoss, VarifocalLoss,
+    SigmoidFocalLoss under ATSS).  MultiboxLoss hands these losses no mask at all for it (the kernels test the class column)."""
+    _lib.require_cuda(target_classes)
+    cls, stride = _class_column(target_classes)
+    B, A = target_classes.shape[:2]
+    mask = torch.empty((B, A), dtype=torch.uint8, device=target_classes.device)
+    _lib.check(_lib.lib().ssdk_valid_sampler(cls.data_ptr(), stride, B, A, _lib.ptr(mask), _lib.current_stream()),
+               'ssdk_valid_sampler')
     return mask.bool()
 
 
