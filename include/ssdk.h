@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 125
+#define SSDK_VERSION 126
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -814,6 +814,26 @@ int ssdk_mean_average_precision(const float* predictions, long long n_pred, cons
                                 const int* gt_offsets, int num_images, long long total_gt, int num_classes,
                                 float iou_threshold, int voc, float* ap_out, double* map_out, void* workspace,
                                 size_t workspace_bytes, void* stream);
+/* The same call with the integer quantities behind the mean (ABI 126; each may be NULL; same workspace size):
+ *   order_out   DEV uint32 [n_pred]: prediction rows in (class ascending, score descending, row ascending) order -- the order of the
+ *               per-class cumulative counts; rows of a foreign class (c < 0 or c >= num_classes) come last, in row order.  -0.0 and
+ *               +0.0 are one score (the reference's comparison): they tie and fall back to row order.
+ *   outcome_out DEV uint8 [n_pred], indexed by prediction row: 0 = neither counter moves (a hit on a difficult box, or a foreign
+ *               class), 1 = true positive, 2 = false positive.
+ * ssdk_mean_average_precision forwards here with two NULLs. */
+int ssdk_mean_average_precision_ex(const float* predictions, long long n_pred, const float* gt_rows, int gt_stride,
+                                   const int* gt_offsets, int num_images, long long total_gt, int num_classes,
+                                   float iou_threshold, int voc, float* ap_out, double* map_out, uint32_t* order_out,
+                                   uint8_t* outcome_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The stable LSD radix sort both orders above are made with, on its own: (uint64 key, uint32 value) pairs, ascending on key bits
+ * [0, end_bit) -- higher bits are ignored -- equal keys keep their input order.  All four arrays DEV [n].  keys / vals are NOT
+ * modified: they are staged in the workspace first, so keys_out == keys (and vals_out == vals) is allowed.
+ * SSDK_E_INVALID for n < 0, n >= 2^31, end_bit outside 1..64 or a null array with n > 0; SSDK_E_WORKSPACE for a missing or too small
+ * workspace (ssdk_sort_pairs_u64_workspace_bytes(n); 0 for an n that is refused).  A refused call launches nothing and writes nothing. */
+size_t ssdk_sort_pairs_u64_workspace_bytes(long long n);
+int ssdk_sort_pairs_u64(const uint64_t* keys, const uint32_t* vals, long long n, int end_bit, uint64_t* keys_out, uint32_t* vals_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -184,6 +184,11 @@ _SIGNATURES = {
     'ssdk_mean_average_precision_workspace_bytes': (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int]),
     'ssdk_mean_average_precision': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
                                               C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'ssdk_mean_average_precision_ex': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
+                                                 C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p]),
+    'ssdk_sort_pairs_u64_workspace_bytes': (C.c_size_t, [C.c_longlong]),
+    'ssdk_sort_pairs_u64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 

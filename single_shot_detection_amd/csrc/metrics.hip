@@ -57,9 +57,10 @@ static MapWs carve_map(void* base, long long n, long long total_gt, int num_clas
     return w;
 }
 
-// order-preserving map of a float onto unsigned, inverted: ascending key = descending score
+// order-preserving map of a float onto unsigned, inverted: ascending key = descending score.  -0.0 + 0.0 = +0.0: the two zeros compare
+// equal in the reference's sort (and the oracle's), so they share one key and fall back to row order
 __device__ __forceinline__ unsigned desc_key(float s) {
-    const unsigned u = __float_as_uint(s);
+    const unsigned u = __float_as_uint(s + 0.0f);
     return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
 }
 
@@ -260,6 +261,7 @@ struct SortPass {
     unsigned* vout;
     long long n;
     int shift, tile, nblocks;
+    unsigned mask;          // 255, or fewer low bits for the top digit when end_bit is no multiple of 8: key bits >= end_bit are ignored
     unsigned* table;        // [256][nblocks]
     unsigned* digit_total;  // [256]
 };
@@ -269,7 +271,7 @@ __global__ void __launch_bounds__(kSortThreads) radix_hist_kernel(SortPass a) {
     s_hist[threadIdx.x] = 0;
     __syncthreads();
     const long long b0 = (long long)blockIdx.x * a.tile, b1 = min(a.n, b0 + a.tile);
-    for (long long i = b0 + threadIdx.x; i < b1; i += kSortThreads) atomicAdd(&s_hist[(unsigned)(a.kin[i] >> a.shift) & 255u], 1u);
+    for (long long i = b0 + threadIdx.x; i < b1; i += kSortThreads) atomicAdd(&s_hist[(unsigned)(a.kin[i] >> a.shift) & a.mask], 1u);
     __syncthreads();
     a.table[(size_t)threadIdx.x * a.nblocks + blockIdx.x] = s_hist[threadIdx.x];
 }
@@ -308,7 +310,7 @@ __global__ void __launch_bounds__(kSortThreads) radix_scatter_kernel(SortPass a)
     const long long b0 = (long long)blockIdx.x * a.tile, b1 = min(a.n, b0 + a.tile);
     const long long quarter = a.tile / 4;
     const long long w0 = b0 + wave * quarter, w1 = min(b1, w0 + quarter);
-    for (long long i = w0 + lane; i < w1; i += kWave) atomicAdd(const_cast<unsigned*>(&s_wcnt[wave][(unsigned)(a.kin[i] >> a.shift) & 255u]), 1u);
+    for (long long i = w0 + lane; i < w1; i += kWave) atomicAdd(const_cast<unsigned*>(&s_wcnt[wave][(unsigned)(a.kin[i] >> a.shift) & a.mask]), 1u);
     __syncthreads();
     {   // thread d: the four waves' starting slots for digit d
         unsigned run = s_base[tid];
@@ -319,7 +321,7 @@ __global__ void __launch_bounds__(kSortThreads) radix_scatter_kernel(SortPass a)
         const long long i = i0 + lane;
         const bool valid = i < w1;
         const unsigned long long key = valid ? a.kin[i] : 0ull;
-        const unsigned d = (unsigned)(key >> a.shift) & 255u;
+        const unsigned d = (unsigned)(key >> a.shift) & a.mask;
         unsigned long long m = __ballot(valid);
 #pragma unroll
         for (int bit = 0; bit < 8; ++bit) {
@@ -369,6 +371,7 @@ static int radix_sort_pairs(unsigned long long* ka, unsigned long long* kb, unsi
     const int passes = (digits & 1) ? digits : digits + 1;
     for (int p = 0; p < passes; ++p) {
         a.shift = 8 * (p < digits ? p : digits - 1);
+        a.mask = (a.shift + 8 > end_bit) ? (1u << (end_bit - a.shift)) - 1u : 255u;
         a.kin = (p & 1) ? kb : ka; a.kout = (p & 1) ? ka : kb;
         a.vin = (p & 1) ? vb : va; a.vout = (p & 1) ? va : vb;
         hipLaunchKernelGGL(radix_hist_kernel, dim3(a.nblocks), dim3(kSortThreads), 0, s, a);
@@ -386,10 +389,53 @@ extern "C" size_t ssdk_mean_average_precision_workspace_bytes(long long n_pred, 
     return carve_map(nullptr, n_pred, total_gt, num_classes).total;
 }
 
+// the u64 / u32 pair sort on its own: keys and vals are staged in the workspace (radix_sort_pairs overwrites its input buffers), so the
+// caller's inputs stay as they were and may even be the outputs
+struct SortWs { unsigned long long* key; unsigned* val; unsigned* table; unsigned* digit_total; size_t total; };
+static SortWs carve_sort(void* base, long long n) {
+    Carver c(base);
+    SortWs w;
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    w.key = c.take<unsigned long long>(nn);
+    w.val = c.take<unsigned>(nn);
+    w.table = c.take<unsigned>((size_t)256 * kSortMaxBlocks);
+    w.digit_total = c.take<unsigned>(256);
+    w.total = c.off;
+    return w;
+}
+
+extern "C" size_t ssdk_sort_pairs_u64_workspace_bytes(long long n) {
+    if (n < 0 || n >= (1LL << 31)) return 0;
+    return carve_sort(nullptr, n).total;
+}
+
+extern "C" int ssdk_sort_pairs_u64(const uint64_t* keys, const uint32_t* vals, long long n, int end_bit, uint64_t* keys_out, uint32_t* vals_out,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long) && sizeof(uint32_t) == sizeof(unsigned), "key / value widths");
+    SSDK_REQUIRE(n >= 0 && n < (1LL << 31) && end_bit >= 1 && end_bit <= 64, SSDK_E_INVALID, "ssdk_sort_pairs_u64: n=%lld end_bit=%d (0 <= n < 2^31, 1 <= end_bit <= 64)", n,
+                 end_bit);
+    SSDK_REQUIRE(n == 0 || (keys && vals && keys_out && vals_out), SSDK_E_INVALID, "ssdk_sort_pairs_u64: null pointer");
+    const SortWs w = carve_sort(workspace, n);
+    SSDK_REQUIRE(workspace && workspace_bytes >= w.total, SSDK_E_WORKSPACE, "ssdk_sort_pairs_u64: workspace %zu < %zu bytes", workspace_bytes, w.total);
+    if (n == 0) return SSDK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    SSDK_CHECK_HIP(hipMemcpyAsync(w.key, keys, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    SSDK_CHECK_HIP(hipMemcpyAsync(w.val, vals, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    return radix_sort_pairs(w.key, reinterpret_cast<unsigned long long*>(keys_out), w.val, vals_out, n, end_bit, w.table, w.digit_total, s);
+}
+
 extern "C" int ssdk_mean_average_precision(const float* predictions, long long n_pred, const float* gt_rows, int gt_stride,
                                            const int* gt_offsets, int num_images, long long total_gt, int num_classes,
                                            float iou_threshold, int voc, float* ap_out, double* map_out, void* workspace,
                                            size_t workspace_bytes, void* stream) {
+    return ssdk_mean_average_precision_ex(predictions, n_pred, gt_rows, gt_stride, gt_offsets, num_images, total_gt, num_classes, iou_threshold, voc, ap_out,
+                                          map_out, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ssdk_mean_average_precision_ex(const float* predictions, long long n_pred, const float* gt_rows, int gt_stride,
+                                              const int* gt_offsets, int num_images, long long total_gt, int num_classes,
+                                              float iou_threshold, int voc, float* ap_out, double* map_out, uint32_t* order_out,
+                                              uint8_t* outcome_out, void* workspace, size_t workspace_bytes, void* stream) {
     SSDK_REQUIRE(n_pred >= 0 && n_pred < (1LL << 31) && total_gt >= 0 && total_gt < (1LL << 31) && num_images >= 0 && num_classes > 0 && num_classes < (1 << 20),
                  SSDK_E_INVALID, "ssdk_mean_average_precision: n_pred=%lld total_gt=%lld num_images=%d num_classes=%d", n_pred, total_gt, num_images, num_classes);
     SSDK_REQUIRE(gt_stride >= 5 && gt_offsets && ap_out && map_out && (n_pred == 0 || predictions) && (total_gt == 0 || gt_rows), SSDK_E_INVALID,
@@ -420,6 +466,8 @@ extern "C" int ssdk_mean_average_precision(const float* predictions, long long n
         hipLaunchKernelGGL(map_match_kernel, dim3((unsigned)cdiv(n, 128)), dim3(128), 0, s, predictions, n_pred, w.val_b, gt_rows, gt_stride, gt_offsets, num_images,
                            num_classes, iou_threshold, w.matched, w.flag);
         SSDK_CHECK_LAUNCH("map_match_kernel");
+        if (order_out) SSDK_CHECK_HIP(hipMemcpyAsync(order_out, w.perm_b, sizeof(unsigned) * (size_t)n_pred, hipMemcpyDeviceToDevice, s));
+        if (outcome_out) SSDK_CHECK_HIP(hipMemcpyAsync(outcome_out, w.flag, (size_t)n_pred, hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(map_ap_kernel, dim3((unsigned)num_classes), dim3(kMapThreads), 0, s, w.key_b, w.perm_b, n_pred, w.flag, w.total_positive, voc, w.prec, w.rec, ap_out);
     SSDK_CHECK_LAUNCH("map_ap_kernel");

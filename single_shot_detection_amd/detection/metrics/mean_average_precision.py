@@ -12,8 +12,11 @@ from ... import _lib
 DIFFICULT_INDEX = 6   # bf/datasets/detection_dataset.py:15
 
 
-def average_precisions(predictions, gts, num_classes, iou_threshold, voc=False, device=None):
-    """-> (mAP: float, ap: torch.tensor [num_classes] on the host, NaN for classes without counted ground truth)"""
+def average_precisions(predictions, gts, num_classes, iou_threshold, voc=False, device=None, details=False):
+    """-> (mAP: float, ap: torch.tensor [num_classes] on the host, NaN for classes without counted ground truth)
+    ``details=True`` -> (mAP, ap, order, outcome), both on the host (``ssdk_mean_average_precision_ex``): order int64 [N] = prediction rows
+    in (class ascending, score descending, row ascending) order, foreign classes last; outcome uint8 [N] by prediction row:
+    0 = neither counter moves, 1 = true positive, 2 = false positive."""
     lib = _lib.lib()
     if device is None:
         device = predictions.device if predictions.is_cuda else torch.device('cuda', torch.cuda.current_device())
@@ -29,10 +32,18 @@ def average_precisions(predictions, gts, num_classes, iou_threshold, voc=False, 
     ws = torch.empty((max(lib.ssdk_mean_average_precision_workspace_bytes(n, total, num_classes), 256),), dtype=torch.uint8, device=device)
     ap = torch.empty((num_classes,), dtype=torch.float32, device=device)
     mean = torch.empty((1,), dtype=torch.float64, device=device)
-    _lib.check(lib.ssdk_mean_average_precision(_lib.ptr(pred), n, _lib.ptr(rows), stride, _lib.ptr(offs), len(gts), total, num_classes,
-                                               float(iou_threshold), int(bool(voc)), _lib.ptr(ap), _lib.ptr(mean), _lib.ptr(ws), ws.numel(),
-                                               _lib.current_stream()), 'ssdk_mean_average_precision')
-    return float(mean.item()), ap.cpu()
+    if not details:
+        _lib.check(lib.ssdk_mean_average_precision(_lib.ptr(pred), n, _lib.ptr(rows), stride, _lib.ptr(offs), len(gts), total, num_classes,
+                                                   float(iou_threshold), int(bool(voc)), _lib.ptr(ap), _lib.ptr(mean), _lib.ptr(ws), ws.numel(),
+                                                   _lib.current_stream()), 'ssdk_mean_average_precision')
+        return float(mean.item()), ap.cpu()
+    order = torch.empty((n,), dtype=torch.int32, device=device)      # (uint32 on the device; n < 2^31, so the bits are the int32's)
+    outcome = torch.empty((n,), dtype=torch.uint8, device=device)
+    _lib.check(lib.ssdk_mean_average_precision_ex(_lib.ptr(pred), n, _lib.ptr(rows), stride, _lib.ptr(offs), len(gts), total, num_classes,
+                                                  float(iou_threshold), int(bool(voc)), _lib.ptr(ap), _lib.ptr(mean), _lib.ptr(order),
+                                                  _lib.ptr(outcome), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
+               'ssdk_mean_average_precision_ex')
+    return float(mean.item()), ap.cpu(), order.cpu().to(torch.int64), outcome.cpu()
 
 
 def mean_average_precision(predictions, gts, class_labels, iou_threshold, voc=False, verbose=True):
