@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 126
+#define SSDK_VERSION 127
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -834,6 +834,50 @@ int ssdk_mean_average_precision_ex(const float* predictions, long long n_pred, c
 size_t ssdk_sort_pairs_u64_workspace_bytes(long long n);
 int ssdk_sort_pairs_u64(const uint64_t* keys, const uint32_t* vals, long long n, int end_bit, uint64_t* keys_out, uint32_t* vals_out,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- integral box head + Distribution Focal Loss (Generalized Focal Loss, arXiv:2006.04388; ABI 127; not in the reference) ----------
+ *
+ * Shapes.  bins = reg_max + 1, 2 <= bins <= 64.  The loc logits are z [B, A, 4, bins] (a row of 4 * bins floats per anchor); side
+ * k = 0..3 is the encoded coordinate tx, ty, tw, th of box_coder.py:22-30 (xy_scale, wh_scale, eps; the in-place form).
+ * Value grid.  v_k[i] = -L_k + i * (2 L_k / reg_max), L_k = xy_limit for k = 0, 1 and wh_limit for k = 2, 3.
+ * Integral.  p = softmax(z[b, a, k, :]) with the row maximum subtracted first; loc[b, a, k] = sum_i p_i v_k[i].  locs [B, A*4] is an
+ * ordinary encoded loc tensor: ssdk_multibox_loss_fwd, ssdk_decode_box and ssdk_postprocess take it as it is.
+ * DFL.  On positive rows only (class != 0 && class != -1, as the box terms).  t_k = the row's encoded target, from its RAW corners and
+ * its anchor, op for op as ssdk_multibox_loss_fwd encodes it; y = fminf(fmaxf((t_k + L_k) / step_k, 0), reg_max);
+ * yl = min(floor(y), reg_max - 1), yr = yl + 1; the side's term is lse(z) - ((yr - y) z[yl] + (y - yl) z[yr]); the row's term is the
+ * mean of its four sides, not weighted by target column 5 (like the box terms); the batch value is
+ * distribution_weight * sum / max(1, #positives).  The clamp is DFL's alone: the box term on the expectation sees the true target.
+ * Gradients.  dz_i = g_dfl * distribution_weight / (4 max(1, #positives)) * (p_i - (yr - y)[i == yl] - (y - yl)[i == yr])
+ *                  + dloc_k * p_i * (v_k[i] - loc_k); rows that are not positive receive zeros.
+ * No atomics, nothing zero-filled beforehand, every sum in an order fixed by the launch: results repeat bit for bit (run to run, eager
+ * against a replayed HIP graph); ssdk_set_deterministic changes nothing here.
+ * Refused with SSDK_E_INVALID, nothing launched or written: bins outside [2, 64], a limit or scale that is not positive, NULL logits /
+ * locs / dlogits, a target without anchors (or without out), a DFL gradient without the class column; SSDK_E_WORKSPACE for a target
+ * (class column) without a large enough workspace.  New fields are only ever appended to the struct. */
+typedef struct ssdk_integral_params {
+    int bins;
+    float xy_limit, wh_limit;
+    float xy_scale, wh_scale, eps;
+    float distribution_weight; /* 0: integral regression alone -- the positives are still counted, the term and y are skipped */
+} ssdk_integral_params;
+size_t ssdk_integral_workspace_bytes(int batch, int num_anchors);
+/* One pass over the logits (+ the one-workgroup sum of the per-workgroup partials when there is a target).
+ *   logits DEV [B, A, 4, bins], 16-byte aligned; anchors DEV [A, 4] or NULL; target DEV [B, A, 6] or NULL (postprocess, evaluation: the
+ *   integral alone; out and the workspace are then neither needed nor touched).
+ *   locs DEV [B, A, 4]; out DEV [2] = (DFL value, #positives as float); workspace: caller-owned, kept until the backward has run --
+ *   it holds each positive row's four y and the divider.
+ * With a target, call it BEFORE ssdk_multibox_loss_fwd, which overwrites the raw corners under the SmoothL1 family; the backward reads
+ * y from the workspace (both directions see the same target) and never reads target columns 0..3. */
+int ssdk_integral_fwd(const ssdk_integral_params* params, const float* logits, const float* anchors, const float* target, int batch,
+                      int num_anchors, float* locs, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* One launch.  dlocs DEV [B, A, 4] or NULL (zeros; no fill launch needed); target_classes DEV: the class column, element r at
+ * target_classes[r * class_stride] (6 for a [B, A, 6] target), or NULL: every row counts as positive and there is no DFL term (the
+ * backward of the integral alone; no workspace); grad_dfl DEV [1]: the upstream gradient of the DFL value, or NULL (0).
+ * dlogits DEV [B, A, 4, bins], 16-byte aligned, written densely: a tile of rows without a positive is stored as zeros without reading
+ * its logits; a positive row's logits are read once. */
+int ssdk_integral_bwd(const ssdk_integral_params* params, const float* logits, const float* dlocs, const float* target_classes,
+                      int class_stride, const float* grad_dfl, int batch, int num_anchors, float* dlogits, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

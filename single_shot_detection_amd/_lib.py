@@ -189,6 +189,11 @@ _SIGNATURES = {
                                                  C.c_void_p]),
     'ssdk_sort_pairs_u64_workspace_bytes': (C.c_size_t, [C.c_longlong]),
     'ssdk_sort_pairs_u64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'ssdk_integral_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'ssdk_integral_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    'ssdk_integral_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
 }
 
 
@@ -218,6 +223,12 @@ class LossParams(C.Structure):
 class _LossParams125(LossParams):
     """ssdk_loss_params as of ABI 125: ``quality_from_iou`` behind the older fields (the fifteenth positional argument)."""
     _fields_ = [('quality_from_iou', C.c_int)]
+
+
+class IntegralParams(C.Structure):
+    """ssdk_integral_params (include/ssdk.h)."""
+    _fields_ = [('bins', C.c_int), ('xy_limit', C.c_float), ('wh_limit', C.c_float), ('xy_scale', C.c_float), ('wh_scale', C.c_float),
+                ('eps', C.c_float), ('distribution_weight', C.c_float)]
 
 
 class ConvDesc(C.Structure):

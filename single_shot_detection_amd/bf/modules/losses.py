@@ -217,3 +217,30 @@ class GeneralizedIoULoss(_Loss):  # losses.py:109-114
             raise NotImplementedError('GeneralizedIoULoss.forward on its own has no backward; inside MultiboxLoss it is fused (csrc/loss.hip)')
         loss = 1.0 - box_utils.generalized_iou(boxes, target, cartesian=False)
         return loss.mean() if self.reduction == 'mean' else loss.sum()
+
+
+class DistributionFocalLoss(_Loss):
+    """Distribution Focal Loss (arXiv:2006.04388; not in the reference) on its own: ``prediction`` [rows, reg_max + 1] logits of one
+    discrete distribution per row, ``target`` [rows] positions in bin units; a row's value is the cross-entropy against the two bins that
+    bracket its target, weighted by their distance to it.  Stock torch ops on any device: the name a config looks up and the yardstick
+    of tools/bench_dfl.py.  Inside MultiboxLoss the term is fused into the integral box head's kernels (csrc/integral.hip), which this
+    class only selects."""
+
+    def __init__(self, reduction='mean', reg_max=16, **kwargs):   # (reduction by name: MultiboxLoss's 'sum' survives filter_kwargs)
+        super(DistributionFocalLoss, self).__init__(reduction=reduction, **kwargs)
+        if not 1 <= int(reg_max) <= 63:
+            raise ValueError(f'DistributionFocalLoss: reg_max={reg_max} outside [1, 63]')
+        self.reg_max = int(reg_max)
+
+    def forward(self, prediction, target):
+        import torch.nn.functional as F
+        if prediction.dim() != 2 or prediction.shape[1] != self.reg_max + 1:
+            raise ValueError(f'DistributionFocalLoss: prediction must be [rows, {self.reg_max + 1}]')
+        y = target.to(prediction.dtype).clamp(0, self.reg_max)
+        yl = y.floor().clamp(max=self.reg_max - 1)
+        left = yl.long()
+        loss = (F.cross_entropy(prediction, left, reduction='none') * (yl + 1 - y) +
+                F.cross_entropy(prediction, left + 1, reduction='none') * (y - yl))
+        if self.reduction == 'none':
+            return loss
+        return loss.mean() if self.reduction == 'mean' else loss.sum()

@@ -64,14 +64,19 @@ def get_extras(source_out_channels, use_depthwise=False, layers=(), activation={
 
 
 def get_heads(out_channels, num_boxes, num_classes, initializer={'name': 'normal_', 'args': {'mean': 0, 'std': 0.01}},
-              score_head_bias_init=0.0):
+              score_head_bias_init=0.0, reg_max=None):
     """detector_builder.py:111-137.  The parameters are ordinary nn.Conv2d weights/biases (state_dict keys
-    ``heads.<i>.score|loc.weight|bias``) kept in channels_last memory = the [n][ky][kx][cin] rows the GEMM reads."""
+    ``heads.<i>.score|loc.weight|bias``) kept in channels_last memory = the [n][ky][kx][cin] rows the GEMM reads.
+    ``reg_max`` (not in the reference): the integral box head of IntegralBoxCoder -- every loc convolution gets nb * 4 * (reg_max + 1)
+    output channels, one distribution per box coordinate."""
+    bins = 1 if reg_max is None else int(reg_max) + 1
+    if reg_max is not None and not 2 <= bins <= 64:
+        raise ValueError(f'heads: reg_max={reg_max} outside [1, 63]')
     initializer_ = functools.partial(getattr(nn.init, initializer['name']), **initializer.get('args', {}))
     heads = nn.ModuleList()
     for in_channels, nb in zip(out_channels, num_boxes):
         score_head = nn.Conv2d(in_channels, nb * num_classes, kernel_size=3, padding=1, bias=True)
-        loc_head = nn.Conv2d(in_channels, nb * 4, kernel_size=3, padding=1, bias=True)
+        loc_head = nn.Conv2d(in_channels, nb * 4 * bins, kernel_size=3, padding=1, bias=True)
         initializer_(score_head.weight)
         nn.init.constant_(score_head.bias, score_head_bias_init)
         initializer_(loc_head.weight)
@@ -79,6 +84,7 @@ def get_heads(out_channels, num_boxes, num_classes, initializer={'name': 'normal
         for m in (score_head, loc_head):
             m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last)
         heads.append(nn.ModuleDict({'score': score_head, 'loc': loc_head}))
+    heads.reg_max = None if reg_max is None else int(reg_max)   # (multi_level_heads: the loc heads' own route)
     return heads
 
 

@@ -11,7 +11,7 @@ from ..bf import base as base_builder
 from ..utils import filter_kwargs
 from . import detector_builder
 from . import sampler as _sampler_mod
-from .box_coder import BoxCoder
+from .box_coder import BoxCoder, build_box_coder  # noqa: F401
 from .detector_wrapper import DetectorWrapper
 from .losses.multibox_loss import MultiboxLoss
 from .postprocessor import Postprocessor
@@ -69,7 +69,7 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
     kwargs = {k: v for k, v in sampler_args.items() if k in sampler.__code__.co_varnames and not k.startswith('_')}
     sampler = functools.partial(sampler, **kwargs)
 
-    box_coder = BoxCoder(**box_coder_args)
+    box_coder = build_box_coder(box_coder_args)
     criterion = MultiboxLoss(sampler=sampler, box_coder=box_coder, **loss_args)
     postprocessor = Postprocessor(box_coder, **postprocess_args)
     target_assigner = build_target_assigner(target_assigner_args)

@@ -129,10 +129,28 @@ class MultiboxLoss(nn.Module):
                  classification_loss,
                  localization_loss,
                  classification_weight=1.0,
-                 localization_weight=1.0):
+                 localization_weight=1.0,
+                 distribution_loss=None,
+                 distribution_weight=0.25):
         super(MultiboxLoss, self).__init__()
         self.sampler = sampler
         self.box_coder = box_coder
+
+        # the integral box head (IntegralBoxCoder: pred[1] holds 4 * bins logits per anchor) and its Distribution Focal Loss, which runs
+        # inside the integral's kernels (csrc/integral.hip); without distribution_loss the head is integral regression alone (weight 0)
+        self.integral = hasattr(box_coder, 'integrate_with_target')
+        self.distribution_loss = None
+        self.distribution_weight = 0.0
+        if distribution_loss is not None:
+            if not isinstance(distribution_loss, dict) or distribution_loss.get('name') != 'DistributionFocalLoss':
+                raise ValueError(f"distribution_loss: {distribution_loss!r}, expected {{'name': 'DistributionFocalLoss'}}")
+            if not self.integral:
+                raise ValueError('distribution_loss needs an IntegralBoxCoder (the loc head must predict distributions)')
+            self.distribution_loss = get_ctor(losses, 'DistributionFocalLoss')(reduction='sum', **{'reg_max': box_coder.reg_max, **distribution_loss})
+            if self.distribution_loss.reg_max != box_coder.reg_max:
+                raise ValueError(f'distribution_loss: reg_max={self.distribution_loss.reg_max}, the box coder has {box_coder.reg_max}')
+            self.distribution_weight = float(distribution_weight)
+        self.last_distribution_loss = None
 
         # multibox_loss.py:23-30 -- same constructor dance, so the same keywords survive filter_kwargs
         ClassificationLoss = get_ctor(losses, classification_loss['name'])
@@ -239,7 +257,7 @@ class MultiboxLoss(nn.Module):
         Args:
             pred: tuple of
                 torch.tensor(:shape [Batch, AnchorBoxes * Classes])
-                torch.tensor(:shape [Batch, AnchorBoxes * 4])
+                torch.tensor(:shape [Batch, AnchorBoxes * 4])  -- with an IntegralBoxCoder: [Batch, AnchorBoxes * 4 * bins] logits
             target: torch.tensor(:shape [Batch, AnchorBoxes, 6])  -- columns 0..3 are overwritten with the encoded
                 regression targets, exactly like multibox_loss.py:81-82
         Returns:
@@ -252,6 +270,15 @@ class MultiboxLoss(nn.Module):
         scores = scores.float().contiguous()
         locs = locs.float().contiguous()
         anchors = anchors.float().contiguous()
+        dfl = None
+        if self.integral:   # the integral node sees the RAW target first: _MultiboxLossFn may encode it in place
+            if locs.dim() != 2 or locs.shape[1] != anchors.shape[0] * 4 * self.box_coder.bins:
+                raise ValueError(f'IntegralBoxCoder: pred[1] of shape {tuple(locs.shape)} is not [Batch, AnchorBoxes * 4 * {self.box_coder.bins}]')
+            locs, dfl = self.box_coder.integrate_with_target(locs, anchors, target, self.distribution_weight)
         loss, class_loss, loc_loss, mask = _MultiboxLossFn.apply(scores, locs, anchors, target, self)
         self.last_sampled_mask = mask
+        if dfl is not None:
+            self.last_distribution_loss = dfl.detach()
+            if self.distribution_weight != 0.0:
+                loss, loc_loss = loss + dfl, loc_loss + dfl
         return loss, class_loss, loc_loss

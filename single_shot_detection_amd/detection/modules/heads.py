@@ -414,7 +414,10 @@ def multi_level_heads_split(sources, heads, split, run_tail, side_stream=None, m
 def multi_level_heads(sources_score, sources_loc, heads):
     """heads: nn.ModuleList of nn.ModuleDict({'score': Conv2d, 'loc': Conv2d}) (detector_builder.py:111-137).
     When the score and loc towers feed different maps (SharedConvPredictor) the two convs of a level run as two
-    single-head GEMMs; otherwise they are fused along N."""
+    single-head GEMMs; otherwise they are fused along N.  Heads built with ``reg_max`` (the integral box head: nb * 4 * bins loc channels)
+    take a route of their own, see _integral_heads."""
+    if getattr(heads, 'reg_max', None) is not None:
+        return _integral_heads(sources_score, sources_loc, heads)
     args = []
     split = []
     for head, xs, xl in zip(heads, sources_score, sources_loc):
@@ -436,4 +439,26 @@ def multi_level_heads(sources_score, sources_loc, heads):
     hints = tuple(head['loc'].weight.shape[0] // 4 for head in heads)
     scores, _ = _HeadsFn.apply(hints, *s_args)
     locs, _ = _HeadsFn.apply(hints, *l_args)
+    return scores, locs
+
+
+def _integral_heads(sources_score, sources_loc, heads):
+    """The ``reg_max`` route: the score heads are the existing single-head pass (n_loc = 0; the anchor types per pixel as the hint); the
+    loc convolutions, whose width the fused head GEMM's anchor-row forms do not know, run on the generic grouped GEMM (ops.conv2d_group,
+    at most 8 levels per launch) and their channels_last outputs -- [B, H, W, nb * 4 * bins] in memory, the order of the logits -- are
+    flattened and concatenated to [B, A * 4 * bins].  (The concatenation is one extra copy of the logits)"""
+    from ... import ops
+    bins = heads.reg_max + 1
+    s_args = []
+    for head, xs in zip(heads, sources_score):
+        empty_w = head['score'].weight.new_zeros((0,) + tuple(head['score'].weight.shape[1:]))
+        s_args += [xs, head['score'].weight, head['score'].bias, empty_w, None]
+    hints = tuple(head['loc'].weight.shape[0] // (4 * bins) for head in heads)
+    scores, _ = _HeadsFn.apply(hints, *s_args)
+    xl, convs = [to_nhwc(x) for x in sources_loc], [head['loc'] for head in heads]
+    outs = []
+    for i in range(0, len(convs), 8):
+        outs += ops.conv2d_group(xl[i:i + 8], convs[i:i + 8])
+    B = outs[0].shape[0]
+    locs = torch.cat([y.permute(0, 2, 3, 1).reshape(B, -1) for y in outs], dim=1)
     return scores, locs

@@ -40,6 +40,8 @@ class Postprocessor(object):
         num_priors = priors.size(0)
         b_scores = b_scores.float().contiguous()   # postprocessor.py:39-40
         b_boxes = b_boxes.float().contiguous()
+        if hasattr(self.box_coder, 'integrate'):   # IntegralBoxCoder: the loc head's distributions -> encoded locs (ssdk_integral_fwd, no target)
+            b_boxes = self.box_coder.integrate(b_boxes.detach(), num_priors)
         priors = priors.float().contiguous()
         num_classes = b_scores.numel() // (batch_size * num_priors)
         softmax = 1 if self.score_converter == 'SOFTMAX' else 0
