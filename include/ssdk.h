@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 127
+#define SSDK_VERSION 128
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -231,6 +231,40 @@ size_t ssdk_encode_ground_truth_atss_workspace_bytes(int batch, int total_gt, in
 int ssdk_encode_ground_truth_atss(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
                                   const float* anchors, int num_anchors, const int32_t* level_sizes, int n_levels, int topk,
                                   float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes, void* stream);
+
+#define SSDK_TAL_MAX_TOPK 32
+size_t ssdk_encode_ground_truth_tal_workspace_bytes(int batch, int total_gt, int topk);
+/*
+ * Target assignment by Task Alignment Learning (TOOD, arXiv:2108.07755 section 3.2; ABI 128; the reference has no such assigner).  An
+ * anchor is positive for a box when its OWN prediction agrees with the box, and the classifier's target is that agreement.  gt_rows,
+ * gt_stride, gt_offsets, batch, total_gt, anchors, target, box_idx as for ssdk_encode_ground_truth; beside them
+ *   scores      DEV [batch, A, num_columns] class LOGITS in the sigmoid layout (class k is column k - 1), num_columns >= 1
+ *   locs        DEV [batch, A, 4] encoded boxes (16-byte aligned, as the anchors)
+ *   xy_scale, wh_scale   the box coder's
+ *   topk        candidates per box, 1..SSDK_TAL_MAX_TOPK; alpha, beta: finite, >= 0 (TOOD: 1 and 6)
+ * The predictions are only read: constants of the step.  For every box g = (x1, y1, x2, y2, class, score) of an image and every anchor
+ * a = (cx, cy, w, h), all arithmetic in fp32, one operation at a time, nothing contracted:
+ *   1. P_a = corners of (cx + w * tx / xy_scale, cy + h * ty / xy_scale, w * expf(tw / wh_scale), h * expf(th / wh_scale)): the decoded
+ *      prediction of ssdk_multibox_loss_*'s GIoU term and of the soft-target losses' quality.
+ *   2. u(a, g) = the plain IoU of P_a with (x1, y1, x2, y2), exactly the quality q of the soft-target losses: inter / union, clamped to
+ *      [0, 1], 0 where the union is not positive or the quotient is not finite.
+ *   3. s(a, g) = 1 / (1 + __expf(-scores[a, k - 1])) with k = (int)class; 0 when class is not within 1..num_columns (NaN included).
+ *   4. a is INSIDE g when x1 < cx < x2 and y1 < cy < y2: the anchor's own centre, as rule 4 of ssdk_encode_ground_truth_atss; NaN is
+ *      never inside.
+ *   5. m(a, g) = s^alpha * u^beta.  x^e is 1 for e == 0 (also 0^0), x for 1, x * x for 2; u^6 is (u * u)^3 = u2 * u2 * u2; every other
+ *      exponent is one __powf(x, e).  A NaN m counts as below every number in rules 6 and 8.
+ *   6. The candidates of g are its min(topk, #inside) inside anchors of largest m, ties to the lower anchor index.  A box without an
+ *      inside anchor has no candidate.
+ *   7. An anchor that is a candidate of several boxes goes to the one with the largest u, then the lowest box index.
+ *   8. Over the anchors g kept after rule 7: m_max = max m, u_max = max u, t(a) = m(a, g) / (m_max + 1e-9f) * u_max.
+ * box_idx[a] = g for a kept anchor, its target row the box's columns 0..4 and score * t(a) in column 5; every other anchor:
+ * SSDK_NOT_MATCHED and (0, 0, 0, 0, 0, 1).  No ignore band and no force stage.  Three launches, nothing [G, A]-shaped, no atomics, no
+ * host synchronisation, the same bits run to run; the call may sit in a captured HIP graph.
+ */
+int ssdk_encode_ground_truth_tal(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                 const float* anchors, int num_anchors, const float* scores, int num_columns, const float* locs,
+                                 float xy_scale, float wh_scale, int topk, float alpha, float beta, float* target, int32_t* box_idx,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- sampler + loss (S1 + L1 + L2 + L3) ----------------------------------------------------------------------- */
 

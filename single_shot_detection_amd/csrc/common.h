@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -78,6 +79,21 @@ __device__ __forceinline__ float iou_corner(float4 a, float area_a, float4 b, fl
 // bf/utils/box_utils.py:16-23 to_corners
 __device__ __forceinline__ float4 to_corners(float4 c) {
     return make_float4(c.x - c.z / 2.0f, c.y - c.w / 2.0f, c.x + c.z / 2.0f, c.y + c.w / 2.0f);
+}
+
+// decoded corner box of a prediction (box_coder.py:55-57 + box_utils.py:16-23); cen returns the centroid form
+__device__ __forceinline__ float4 decode_corners(float4 t, float4 p, float xy_scale, float wh_scale, float4& cen) {
+    cen = make_float4(p.x + p.z * t.x / xy_scale, p.y + p.w * t.y / xy_scale, p.z * expf(t.z / wh_scale), p.w * expf(t.w / wh_scale));
+    return to_corners(cen);
+}
+
+// the quality of a positive (include/ssdk.h: the soft-target losses and the task-aligned assigner): plain IoU of predicted corners P against target corners T, in [0, 1], 0 when undefined
+__device__ __forceinline__ float box_quality(float4 P, float4 T) {
+    const float inter = area4(tmaxf(P.x, T.x), tmaxf(P.y, T.y), tminf(P.z, T.z), tminf(P.w, T.w));
+    const float uni = area4(P.x, P.y, P.z, P.w) + area4(T.x, T.y, T.z, T.w) - inter;
+    const float q = inter / uni;
+    if (!(uni > 0.0f) || !(fabsf(q) <= FLT_MAX)) return 0.0f;
+    return fminf(fmaxf(q, 0.0f), 1.0f);
 }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }

@@ -388,11 +388,8 @@ __device__ __forceinline__ float soft_t(int c, int pos, float s, int C, float ep
     return c == pos ? s - eps * s : eps * s / (float)(C - 1);
 }
 
-// decoded corner box of a prediction (box_coder.py:55-57 + box_utils.py:16-23); cen returns the centroid form
-__device__ __forceinline__ float4 decode_corners(float4 t, float4 p, float xy_scale, float wh_scale, float4& cen) {
-    cen = make_float4(p.x + p.z * t.x / xy_scale, p.y + p.w * t.y / xy_scale, p.z * expf(t.z / wh_scale), p.w * expf(t.w / wh_scale));
-    return to_corners(cen);
-}
+// (decode_corners, the decoded corner box of a prediction, and box_quality, the plain IoU of the soft-target losses, live in common.h:
+// the task-aligned assigner of match.hip computes both)
 
 // 1 - generalized_iou (box_utils.py:104-143, cartesian=False) of predicted corners P against target corners T
 __device__ __forceinline__ float giou_loss(float4 P, float4 T) {
@@ -763,15 +760,6 @@ __device__ __forceinline__ float pow_small(float b, float g) {
     if (g == 1.0f) return b;
     if (g == 0.0f) return 1.0f;
     return __powf(b, g);
-}
-
-// the quality of a positive (include/ssdk.h): plain IoU of predicted corners P against target corners T, in [0, 1], 0 when undefined
-__device__ __forceinline__ float box_quality(float4 P, float4 T) {
-    const float inter = area4(tmaxf(P.x, T.x), tmaxf(P.y, T.y), tminf(P.z, T.z), tminf(P.w, T.w));
-    const float uni = area4(P.x, P.y, P.z, P.w) + area4(T.x, T.y, T.z, T.w) - inter;
-    const float q = inter / uni;
-    if (!(uni > 0.0f) || !(fabsf(q) <= FLT_MAX)) return 0.0f;
-    return fminf(fmaxf(q, 0.0f), 1.0f);
 }
 
 // one element of the sigmoid-target kinds, target y: the value, or (GRAD) d value / dx  (include/ssdk.h)

@@ -20,6 +20,9 @@
 // Beside it (ssdk_encode_ground_truth_atss; not in the reference): Adaptive Training Sample Selection, two launches of its own --
 // atss_candidates_kernel (one workgroup per (box, level): the level's k nearest anchors as a cutoff key, their IoUs) and
 // atss_assign_kernel (assign_kernel's shape with the box's own threshold in place of the two fixed ones); see further down.
+// And ssdk_encode_ground_truth_tal (not in the reference either): Task Alignment Learning, three launches of its own -- tal_candidates_kernel (one
+// workgroup per box: the topk inside anchors of largest s^alpha * u^beta, from the anchors' own predictions), tal_assign_kernel and
+// tal_normalise_kernel (one wave per box: column 5 of the rows the box kept); see further down.
 // IoU is computed op for op like the reference (this TU is built -ffp-contract=off, IEEE divide) so that
 // assignments are bit-exact.
 #include "common.h"
@@ -555,6 +558,217 @@ __global__ void __launch_bounds__(kAssignThreads) atss_assign_kernel(const float
     write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
 }
 
+// ---- Task Alignment Learning (TOOD, arXiv:2108.07755 section 3.2; not in the reference) ---------------------------------------------------
+// Per box: among the anchors whose centre lies strictly inside it, the topk of largest m = s^alpha * u^beta are its candidates -- s the
+// anchor's own predicted probability of the box's class, u the IoU of the anchor's own decoded box with it; an anchor that is a candidate
+// of several boxes goes to the largest u, then the lowest box index; column 5 of a kept anchor is score * m / (m_max + 1e-9) * u_max over
+// the anchors the box kept (include/ssdk.h has the rule operation by operation).  Three launches, nothing [G, A]-shaped, no atomics,
+// nothing zero-filled by a launch of its own:
+//   1. tal_candidates_kernel  one workgroup per box: ONE sweep of the anchor table (16-byte loads), the inside test first; only an inside
+//                             anchor loads its 16-byte loc and the one logit of the box's class and becomes the key
+//                             (ord_f32(m) << 32 | ~a), larger = better, ties to the lower anchor.  The workgroup pops its kk =
+//                             min(topk, #inside) largest keys and stores the LAST one -- the box's cutoff key -- and the kk candidates
+//                             (anchor, m, u) in rank order, each with a `kept` flag of 0.
+//   2. tal_assign_kernel      one thread per (image, anchor), on the pattern of atss_assign_kernel: it decodes its own box once, recomputes
+//                             its key against each box that holds its centre with the SAME device functions (the bits are launch 1's) and
+//                             is a candidate exactly when key >= cutoff(box).  The winner's row leaves through write_target_rows with the
+//                             box's score in column 5, and the thread raises its `kept` flag in the winner's candidate list.
+//   3. tal_normalise_kernel   one wave per box: m_max and u_max over the box's kept candidates, then column 5 of their rows.  It touches
+//                             total_gt * topk elements, not A.
+// (The kept flag, not box_idx, tells launch 3 which candidates a box kept: box_idx is optional, and a workspace sized without the anchor
+// count has no room for a private copy.  The flag is written by launch 1 and raised by exactly one thread of launch 2: no zero-fill.)
+constexpr int kTalThreads = 1024;
+constexpr int kTalWaves = kTalThreads / kWave;
+constexpr int kTalNormThreads = 256;
+constexpr unsigned long long kTalNoCutoff = ~0ull;   // above every key: a box without an inside anchor has no candidate
+struct TalParams { float xy_scale, wh_scale, alpha, beta; int C; };
+
+// x^e for x >= 0, e >= 0 (rule 5): 0, 1, 2 -- and 6 where `six` allows it, the default beta -- are multiplies, the rest one __powf
+__device__ __forceinline__ float tal_pow(float x, float e, bool six) {
+    if (e == 0.0f) return 1.0f;
+    if (e == 1.0f) return x;
+    if (e == 2.0f) return x * x;
+    if (six && e == 6.0f) { const float x2 = x * x; return x2 * x2 * x2; }
+    return __powf(x, e);
+}
+// column of the box's class in a row of logits, or -1 (rule 3: s = 0)
+__device__ __forceinline__ int tal_class_column(float cls, int C) { return (cls >= 1.0f && cls <= (float)C) ? (int)cls - 1 : -1; }
+// rules 1 - 3 and 5 for one (anchor, box): P the anchor's decoded corners, gb the box's, x the logit of the box's class (has_class: the class
+// is one of the columns).  Both launches call this, and decode_corners, on the same inputs: the same bits.
+__device__ __forceinline__ float tal_metric(float4 P, float4 gb, float x, bool has_class, const TalParams& tp, float& u) {
+    u = box_quality(P, gb);
+    const float s = has_class ? 1.0f / (1.0f + __expf(-x)) : 0.0f;
+    return tal_pow(s, tp.alpha, false) * tal_pow(u, tp.beta, true);
+}
+__device__ __forceinline__ unsigned long long tal_key(float m, int a) { return make_key(ord_f32(m), a); }   // never 0: the low word is ~a >= 2^31
+__device__ __forceinline__ bool tal_inside(float4 gb, float4 p) { return gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w; }
+// image of row g (< gt_off[batch]): the last i with gt_off[i] <= g
+__device__ __forceinline__ int tal_image_of(const int32_t* __restrict__ gt_off, int batch, int g) {
+    int lo = 0, hi = batch - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (gt_off[mid] <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kTalThreads) tal_candidates_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                     int batch, const float4* __restrict__ anchors, int A,
+                                                                     const float* __restrict__ scores, const float4* __restrict__ locs, TalParams tp,
+                                                                     int topk, unsigned long long* __restrict__ cutoff, int* __restrict__ cand_anchor,
+                                                                     float* __restrict__ cand_m, float* __restrict__ cand_u, int* __restrict__ cand_kept) {
+    __shared__ unsigned long long s_red[2][kTalWaves];
+    const int g = blockIdx.x;
+    if (g >= gt_off[batch]) return;   // rows past the last image's are padding (a row buffer of fixed capacity)
+    const int i = tal_image_of(gt_off, batch, g);
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const float* r = gt_rows + (size_t)g * gt_stride;
+    const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
+    const int col = tal_class_column(r[4], tp.C);
+    const size_t row0 = (size_t)i * A;
+    auto metric = [&](int a, const float4& p, float& u) {   // of an inside anchor
+        float4 cen;
+        const float4 P = decode_corners(locs[row0 + a], p, tp.xy_scale, tp.wh_scale, cen);
+        const float x = col >= 0 ? scores[(row0 + a) * tp.C + col] : 0.0f;
+        return tal_metric(P, gb, x, col >= 0, tp, u);
+    };
+    // The sweep: the thread's two largest keys stay in registers (selects, as in atss_candidates_kernel).  0 = no key.
+    unsigned long long k1 = 0ull, k2 = 0ull;
+    auto take = [&](int a, const float4& p) {
+        unsigned long long k = 0ull;
+        if (tal_inside(gb, p)) { float u; k = tal_key(metric(a, p, u), a); }
+        const bool gt1 = k > k1, gt2 = k > k2;
+        k2 = gt1 ? k1 : (gt2 ? k : k2);
+        k1 = gt1 ? k : k1;
+    };
+    int a = threadIdx.x;
+    for (; a + 3 * kTalThreads < A; a += 4 * kTalThreads) {   // four loads in flight
+        const float4 p0 = anchors[a], p1 = anchors[a + kTalThreads], p2 = anchors[a + 2 * kTalThreads], p3 = anchors[a + 3 * kTalThreads];
+        take(a, p0);
+        take(a + kTalThreads, p1);
+        take(a + 2 * kTalThreads, p2);
+        take(a + 3 * kTalThreads, p3);
+    }
+    for (; a < A; a += kTalThreads) take(a, anchors[a]);
+    // Up to topk pops of the workgroup's largest remaining key, one barrier each (the two halves of s_red alternate); the first empty pop
+    // ends them: the box has fewer inside anchors than topk.  The owner of the popped key moves on to its second key; only a thread that
+    // loses both re-reads its own anchors for the next one below the popped key.
+    unsigned long long cur = k1, mine = 0ull, last = kTalNoCutoff;
+    for (int j = 0; j < topk; ++j) {
+        const unsigned long long w = wave_allreduce(cur, OpMaxU64());
+        if (lane == 0) s_red[j & 1][wave] = w;
+        __syncthreads();
+        unsigned long long popped = s_red[j & 1][0];
+#pragma unroll
+        for (int q = 1; q < kTalWaves; ++q) { const unsigned long long t = s_red[j & 1][q]; popped = t > popped ? t : popped; }
+        if (popped == 0ull) break;   // (the same value in every thread)
+        last = popped;
+        if (threadIdx.x == j) mine = popped;   // (topk <= 32: thread j keeps the j-th candidate)
+        if (cur == popped) {
+            if (cur == k1) cur = k2;   // (0 when the thread had a single inside anchor: it has nothing left)
+            else {
+                cur = 0ull;
+                for (int b = threadIdx.x; b < A; b += kTalThreads) {
+                    const float4 p = anchors[b];
+                    if (!tal_inside(gb, p)) continue;
+                    float u;
+                    const unsigned long long k = tal_key(metric(b, p, u), b);
+                    if (k < popped && k > cur) cur = k;
+                }
+            }
+        }
+    }
+    if (threadIdx.x < SSDK_TAL_MAX_TOPK) {   // the candidate list in rank order; the slots past kk say so
+        const size_t slot = (size_t)g * SSDK_TAL_MAX_TOPK + threadIdx.x;
+        int ca = -1;
+        float m = 0.0f, u = 0.0f;
+        if (mine != 0ull) {
+            ca = min(key_col(mine), A - 1);   // (a popped key is always an anchor; the clamp costs nothing)
+            m = metric(ca, anchors[ca], u);
+        }
+        cand_anchor[slot] = ca;
+        cand_m[slot] = m;
+        cand_u[slot] = u;
+        cand_kept[slot] = 0;
+    }
+    if (threadIdx.x == 0) cutoff[g] = last;
+}
+
+__global__ void __launch_bounds__(kAssignThreads) tal_assign_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                    const float4* __restrict__ anchors, int A, const float* __restrict__ scores,
+                                                                    const float4* __restrict__ locs, TalParams tp, const unsigned long long* __restrict__ cutoff,
+                                                                    const int* __restrict__ cand_anchor, int* __restrict__ cand_kept,
+                                                                    float* __restrict__ target, int32_t* __restrict__ box_idx) {
+    __shared__ float4 s_box[kGtChunk];
+    __shared__ int s_col[kGtChunk];
+    __shared__ unsigned long long s_cut[kGtChunk];
+    __shared__ __attribute__((aligned(16))) float s_out[kAssignThreads * 6];
+
+    const int i = blockIdx.y;
+    const int a0 = blockIdx.x * kAssignThreads;
+    const int a = a0 + threadIdx.x;
+    const int g0 = gt_off[i], G = gt_off[i + 1] - g0;
+    const bool live = a < A;
+    const size_t row = (size_t)i * A + (live ? a : 0);
+
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), P = p;
+    if (live && G > 0) {
+        float4 cen;
+        p = anchors[a];
+        P = decode_corners(locs[row], p, tp.xy_scale, tp.wh_scale, cen);
+    }
+    float best = 0.0f;
+    int bi = SSDK_NOT_MATCHED;
+    for (int base = 0; base < G; base += kGtChunk) {
+        const int n = min(kGtChunk, G - base);
+        __syncthreads();
+        if (threadIdx.x < n) {
+            const int g = g0 + base + threadIdx.x;
+            const float* r = gt_rows + (size_t)g * gt_stride;
+            s_box[threadIdx.x] = make_float4(r[0], r[1], r[2], r[3]);
+            s_col[threadIdx.x] = tal_class_column(r[4], tp.C);
+            s_cut[threadIdx.x] = cutoff[g];
+        }
+        __syncthreads();
+        if (live)
+            for (int k = 0; k < n; ++k) {
+                const float4 gb = s_box[k];
+                if (!tal_inside(gb, p)) continue;
+                const int col = s_col[k];
+                const float x = col >= 0 ? scores[row * tp.C + col] : 0.0f;
+                float u;
+                const float m = tal_metric(P, gb, x, col >= 0, tp, u);
+                if (tal_key(m, a) < s_cut[k]) continue;                      // not among the box's topk
+                if (bi < 0 || u > best) { best = u; bi = base + k; }         // rule 7: ascending k, strict >: the lowest box index keeps a tie
+            }
+    }
+    if (bi >= 0) {   // the thread is one of its box's candidates: its slot in the box's list (at most 32 entries, positives only)
+        const size_t slot0 = (size_t)(g0 + bi) * SSDK_TAL_MAX_TOPK;
+        for (int j = 0; j < SSDK_TAL_MAX_TOPK; ++j)
+            if (cand_anchor[slot0 + j] == a) { cand_kept[slot0 + j] = 1; break; }
+    }
+    write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
+}
+
+__global__ void __launch_bounds__(kTalNormThreads) tal_normalise_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                        int batch, int A, const int* __restrict__ cand_anchor,
+                                                                        const float* __restrict__ cand_m, const float* __restrict__ cand_u,
+                                                                        const int* __restrict__ cand_kept, float* __restrict__ target) {
+    const int g = blockIdx.x * (kTalNormThreads / kWave) + (threadIdx.x >> 6);
+    if (g >= gt_off[batch]) return;   // (a whole wave leaves: no barrier in this kernel)
+    const int lane = lane_id();
+    const int i = tal_image_of(gt_off, batch, g);
+    const size_t slot = (size_t)g * SSDK_TAL_MAX_TOPK + (lane < SSDK_TAL_MAX_TOPK ? lane : 0);
+    const int a = lane < SSDK_TAL_MAX_TOPK ? cand_anchor[slot] : -1;
+    const bool kept = a >= 0 && cand_kept[slot] != 0;
+    const float m = kept ? cand_m[slot] : 0.0f, u = kept ? cand_u[slot] : 0.0f;
+    // m >= 0 and u >= 0; fmaxf skips a NaN m (rule 5: below every number)
+    const float m_max = wave_allreduce(m, OpMaxF()), u_max = wave_allreduce(u, OpMaxF());
+    if (!kept) return;
+    const float t = m / (m_max + 1e-9f) * u_max;
+    target[((size_t)i * A + a) * 6 + 5] = gt_rows[(size_t)g * gt_stride + 5] * t;
+}
+
 }  // namespace ssdk
 
 using namespace ssdk;
@@ -759,5 +973,64 @@ extern "C" int ssdk_encode_ground_truth_atss(const float* gt_rows, int gt_stride
     hipLaunchKernelGGL(atss_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors, lv,
                        topk, cutoff, cand_iou, target, box_idx);
     SSDK_CHECK_LAUNCH("atss_assign_kernel");
+    return SSDK_OK;
+}
+
+static inline size_t tal_slots(int total_gt) { return (size_t)(total_gt > 0 ? total_gt : 1); }
+
+extern "C" size_t ssdk_encode_ground_truth_tal_workspace_bytes(int batch, int total_gt, int topk) {
+    (void)batch;
+    (void)topk;   // (a box's list has SSDK_TAL_MAX_TOPK slots whatever topk is: the slot of (box, rank) does not move with it)
+    Carver c(nullptr);
+    c.take<unsigned long long>(tal_slots(total_gt));
+    c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    return c.off;
+}
+
+extern "C" int ssdk_encode_ground_truth_tal(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                            const float* anchors, int num_anchors, const float* scores, int num_columns, const float* locs,
+                                            float xy_scale, float wh_scale, int topk, float alpha, float beta, float* target, int32_t* box_idx,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_tal: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
+    SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: batch exceeds grid limits");
+    SSDK_REQUIRE(gt_offsets && anchors && target && (gt_rows || total_gt == 0), SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: null pointer");
+    SSDK_REQUIRE(scores && locs, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: null scores or locs (the rule reads the anchors' own predictions)");
+    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: gt_stride=%d < 6", gt_stride);
+    SSDK_REQUIRE(num_columns >= 1, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: num_columns=%d < 1", num_columns);
+    SSDK_REQUIRE(topk >= 1 && topk <= SSDK_TAL_MAX_TOPK, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: topk=%d outside 1..%d", topk,
+                 SSDK_TAL_MAX_TOPK);
+    SSDK_REQUIRE(alpha >= 0.0f && alpha <= FLT_MAX && beta >= 0.0f && beta <= FLT_MAX, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_tal: alpha=%g beta=%g must be finite and not negative", (double)alpha, (double)beta);
+    SSDK_REQUIRE((((uintptr_t)anchors | (uintptr_t)locs) & 15) == 0, SSDK_E_UNSUPPORTED,
+                 "ssdk_encode_ground_truth_tal: anchors and locs must be 16-byte aligned");
+    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_tal_workspace_bytes(batch, total_gt, topk), SSDK_E_WORKSPACE,
+                 "ssdk_encode_ground_truth_tal: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    Carver c(workspace);
+    unsigned long long* cutoff = c.take<unsigned long long>(tal_slots(total_gt));
+    int* cand_anchor = c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    float* cand_m = c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    float* cand_u = c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    int* cand_kept = c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
+    TalParams tp;
+    tp.xy_scale = xy_scale; tp.wh_scale = wh_scale; tp.alpha = alpha; tp.beta = beta; tp.C = num_columns;
+    if (total_gt > 0) {
+        hipLaunchKernelGGL(tal_candidates_kernel, dim3(total_gt), dim3(kTalThreads), 0, s, gt_rows, gt_stride, gt_offsets, batch,
+                           (const float4*)anchors, num_anchors, scores, (const float4*)locs, tp, topk, cutoff, cand_anchor, cand_m, cand_u, cand_kept);
+        SSDK_CHECK_LAUNCH("tal_candidates_kernel");
+    }
+    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
+    hipLaunchKernelGGL(tal_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors,
+                       scores, (const float4*)locs, tp, cutoff, cand_anchor, cand_kept, target, box_idx);
+    SSDK_CHECK_LAUNCH("tal_assign_kernel");
+    if (total_gt > 0) {
+        hipLaunchKernelGGL(tal_normalise_kernel, dim3(cdiv(total_gt, kTalNormThreads / kWave)), dim3(kTalNormThreads), 0, s, gt_rows, gt_stride,
+                           gt_offsets, batch, num_anchors, cand_anchor, cand_m, cand_u, cand_kept, target);
+        SSDK_CHECK_LAUNCH("tal_normalise_kernel");
+    }
     return SSDK_OK;
 }

@@ -15,14 +15,15 @@ from .box_coder import BoxCoder, build_box_coder  # noqa: F401
 from .detector_wrapper import DetectorWrapper
 from .losses.multibox_loss import MultiboxLoss
 from .postprocessor import Postprocessor
-from .target_assigner import AtssTargetAssigner, TargetAssigner
+from .target_assigner import AtssTargetAssigner, TargetAssigner, TaskAlignedAssigner
 
-TARGET_ASSIGNERS = {'TargetAssigner': TargetAssigner, 'AtssTargetAssigner': AtssTargetAssigner}
+TARGET_ASSIGNERS = {'TargetAssigner': TargetAssigner, 'AtssTargetAssigner': AtssTargetAssigner, 'TaskAlignedAssigner': TaskAlignedAssigner}
 
 
 def build_target_assigner(args):
     """A config's ``target_assigner`` dict.  ``'name'`` (not in the reference) picks the class, by default ``'TargetAssigner'``, whose
-    keywords the other entries are: ``{'name': 'AtssTargetAssigner', 'topk': 9}`` is the adaptive assigner."""
+    keywords the other entries are: ``{'name': 'AtssTargetAssigner', 'topk': 9}`` is the adaptive assigner, ``{'name': 'TaskAlignedAssigner',
+    'topk': 13}`` the prediction-aware one (``step_fn`` hands it the step's own prediction and the box coder)."""
     args = dict(args)
     name = args.pop('name', 'TargetAssigner')
     if name not in TARGET_ASSIGNERS:
@@ -75,7 +76,9 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
     target_assigner = build_target_assigner(target_assigner_args)
     detector_wrapper = DetectorWrapper(detector, preprocess, postprocessor)
 
-    def encode_ground_truth(ground_truth, priors):
+    def encode_ground_truth(ground_truth, priors, prediction):
+        if isinstance(target_assigner, TaskAlignedAssigner):   # (it ranks the anchors by their own prediction, a constant of the step)
+            return target_assigner.encode_ground_truth(ground_truth, priors, prediction, box_coder)
         if isinstance(target_assigner, AtssTargetAssigner):   # (it selects per pyramid level)
             return target_assigner.encode_ground_truth(ground_truth, priors, level_sizes=detector.anchor_level_sizes(priors))
         return target_assigner.encode_ground_truth(ground_truth, priors)
@@ -102,7 +105,7 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
                 scores, locs, loc_sources = detector.predictor.forward_from_taps(list(t[:n_sources]), t[x_index])
                 priors = detector.generate_anchors(img_like, loc_sources)
                 self.priors = priors
-                target = encode_ground_truth(self.packed, priors)
+                target = encode_ground_truth(self.packed, priors, (scores, locs))
                 loss, class_loss, loc_loss = criterion((scores, locs), priors, target)
                 return loss, class_loss, loc_loss, scores, locs
             params = [p for n, p in detector.predictor.named_parameters() if not n.startswith('features.')]
@@ -128,7 +131,7 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
             prediction, priors = [scores, locs], hot.priors
         else:
             *prediction, priors = detector(imgs)
-            target = encode_ground_truth(ground_truth, priors)
+            target = encode_ground_truth(ground_truth, priors, prediction)
             loss, class_loss, loc_loss = criterion(prediction, priors, target)
         prediction = [x.detach() for x in prediction]
         if phase == 'eval':

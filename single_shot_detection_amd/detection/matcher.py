@@ -3,7 +3,8 @@
 reference's own function on a given weight matrix (``ssdk_match_per_prediction``), ``match_boxes`` the fused form for one box set.
 ``match_bipartite`` (matcher.py:7-31) is the reference's own function on a given matrix too (``ssdk_match_bipartite``); nothing in the
 reference calls it, here it is also the opt-in force stage of the fused path (``TargetAssigner(force_match='bipartite')``).
-``match_atss`` is the one-image form of ``AtssTargetAssigner`` (``ssdk_encode_ground_truth_atss``), which the reference does not have."""
+``match_atss`` is the one-image form of ``AtssTargetAssigner`` (``ssdk_encode_ground_truth_atss``), which the reference does not have;
+``match_task_aligned`` that of ``TaskAlignedAssigner`` (``ssdk_encode_ground_truth_tal``), which it does not have either."""
 import torch
 
 from .. import _lib
@@ -91,3 +92,18 @@ def match_per_prediction(weights, matched_threshold, unmatched_threshold=None, f
                                              int(bool(force_match_for_each_target)), _lib.ptr(box_idx), _lib.ptr(ws), ws.numel(),
                                              _lib.current_stream()), 'ssdk_match_per_prediction')
     return box_idx
+
+
+def match_task_aligned(gt_boxes, gt_classes, anchors, scores, locs, box_coder, topk=13, alpha=1.0, beta=6.0):
+    """box_idx int64 [A] for one image by Task Alignment Learning (``TaskAlignedAssigner``; not in the reference): the box an anchor is
+    positive for, else NOT_MATCHED -- there is no ignore band and no force stage.  ``gt_boxes`` [G, >=4] corner form, ``gt_classes`` [G]
+    (1-based: class k is column k - 1 of the logits), ``anchors`` [A, 4] centroid, ``scores`` [A, C] (or [A * C]) class logits and ``locs``
+    [A, 4] (or [A * 4]) encoded boxes of that image, ``box_coder`` the coder that decodes them."""
+    from .target_assigner import TaskAlignedAssigner
+    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
+    gt[:, :4] = gt_boxes[:, :4]
+    gt[:, 4] = gt_classes.to(gt.device).reshape(-1).float()
+    gt[:, 5] = 1.0
+    _, idx = TaskAlignedAssigner(topk, alpha, beta).encode_ground_truth([gt], anchors, (scores.reshape(1, -1), locs.reshape(1, -1)), box_coder,
+                                                                         return_box_idx=True)
+    return idx[0].long()

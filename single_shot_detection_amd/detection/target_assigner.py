@@ -1,5 +1,5 @@
 """TargetAssigner -- mirror of detection/target_assigner.py:17-63 on libssdk (csrc/match.hip); AtssTargetAssigner, the adaptive assigner
-the reference does not have, beside it."""
+the reference does not have, beside it; and TaskAlignedAssigner, the prediction-aware one of TOOD, which it does not have either."""
 import ctypes
 
 import numpy as np
@@ -196,4 +196,76 @@ class AtssTargetAssigner(object):
                    'ssdk_encode_ground_truth_atss')
         # keep the staging tensors alive until the stream has consumed them
         target._ssdk_keepalive = (rows, offs)
+        return (target, box_idx) if return_box_idx else target
+
+
+TAL_MAX_TOPK = 32      # SSDK_TAL_MAX_TOPK (include/ssdk.h)
+
+
+class TaskAlignedAssigner(object):
+    """Task Alignment Learning (TOOD, arXiv:2108.07755 section 3.2; not in the reference): the prediction-aware assigner of TOOD,
+    PP-YOLOE and YOLOv6/v8.  An anchor is a candidate of a box when its centre lies strictly inside the box and its alignment
+    ``m = s^alpha * u^beta`` -- ``s`` its OWN predicted probability of the box's class (sigmoid layout: class k is column k - 1), ``u``
+    the IoU of its OWN decoded box with the box -- is among the ``topk`` largest of the box; a candidate of several boxes goes to the
+    largest ``u``, then the lowest box index.  Column 5 of a positive row is ``score * m / (m_max + 1e-9) * u_max`` over the anchors its
+    box kept: the soft target of ``QualityFocalLoss`` / ``VarifocalLoss`` with ``use_iou=False``.  There is no ignore band and NO force
+    stage: a box without an anchor centre inside has no positive anchor.  The predictions are constants of the step (detached here;
+    nothing has a gradient).  The exact rule, operation by operation: ``ssdk_encode_ground_truth_tal`` in include/ssdk.h."""
+
+    def __init__(self, topk=13, alpha=1.0, beta=6.0):
+        if isinstance(topk, bool) or int(topk) != topk or not 1 <= topk <= TAL_MAX_TOPK:
+            raise ValueError(f'TaskAlignedAssigner: topk={topk!r}, expected an integer in 1..{TAL_MAX_TOPK}')
+        for name, v in (('alpha', alpha), ('beta', beta)):
+            try:
+                ok = not isinstance(v, str) and 0.0 <= float(v) < float('inf')
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f'TaskAlignedAssigner: {name}={v!r}, expected a finite number >= 0')
+        self.topk, self.alpha, self.beta = int(topk), float(alpha), float(beta)
+        self._ws = None
+
+    def encode_ground_truth(self, ground_truth, anchors, prediction, box_coder, return_box_idx=False):
+        """Inputs and outputs as ``TargetAssigner.encode_ground_truth``; beside them ``prediction = (scores, locs)`` as the detector returns
+        them (``[Batch, AnchorBoxes * C]`` class logits -- C is taken from the shape -- and ``[Batch, AnchorBoxes * 4]`` encoded boxes) and
+        the ``box_coder`` whose ``xy_scale`` / ``wh_scale`` decode them.  With an ``IntegralBoxCoder`` the loc head's distributions are
+        first integrated (``box_coder.integrate`` under ``no_grad``): one more pass over the loc logits than the loss itself makes."""
+        if prediction is None or len(prediction) != 2:
+            raise ValueError('TaskAlignedAssigner.encode_ground_truth: prediction must be (scores, locs)')
+        if box_coder is None:
+            raise ValueError('TaskAlignedAssigner.encode_ground_truth: box_coder is required (its scales decode the predicted boxes)')
+        scores, locs = prediction
+        _lib.require_cuda(anchors, scores, locs)
+        lib = _lib.lib()
+        device = anchors.device
+        batch_size = len(ground_truth)
+        num_anchors = anchors.size(0)
+        anchors = anchors.contiguous().float()
+        with torch.no_grad():
+            scores, locs = scores.detach(), locs.detach()
+            if hasattr(box_coder, 'integrate'):
+                locs = box_coder.integrate(locs, num_anchors)
+            scores, locs = scores.float().contiguous(), locs.float().contiguous()
+        if scores.shape[0] != batch_size or locs.shape[0] != batch_size or locs.numel() != batch_size * num_anchors * 4:
+            raise ValueError(f'TaskAlignedAssigner.encode_ground_truth: locs of shape {tuple(locs.shape)} / scores of shape '
+                             f'{tuple(scores.shape)} for a batch of {batch_size} and {num_anchors} anchors')
+        num_columns, rest = divmod(scores.numel(), batch_size * num_anchors)
+        if rest or num_columns < 1:
+            raise ValueError(f'TaskAlignedAssigner.encode_ground_truth: scores of shape {tuple(scores.shape)} are not [Batch, {num_anchors} * C]')
+        if isinstance(ground_truth, PackedGroundTruth):
+            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
+        else:
+            rows, offs, total = pack_ground_truth(ground_truth, device)
+        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
+        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
+        need = lib.ssdk_encode_ground_truth_tal_workspace_bytes(batch_size, total, self.topk)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
+        _lib.check(lib.ssdk_encode_ground_truth_tal(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors,
+                                                    _lib.ptr(scores), num_columns, _lib.ptr(locs), float(box_coder.xy_scale),
+                                                    float(box_coder.wh_scale), self.topk, self.alpha, self.beta, _lib.ptr(target),
+                                                    _lib.ptr(box_idx), _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
+                   'ssdk_encode_ground_truth_tal')
+        # keep the staging tensors alive until the stream has consumed them
+        target._ssdk_keepalive = (rows, offs, scores, locs)
         return (target, box_idx) if return_box_idx else target
