@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 128
+#define SSDK_VERSION 129
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -398,6 +398,23 @@ int ssdk_postprocess(const float* scores, const float* locs, const float* priors
                      int soft_nms, float soft_sigma, int max_total, float xy_scale, float wh_scale, float* out, int out_cap,
                      int32_t* counts,
                      int64_t* nms_candidates, void* workspace, size_t workspace_bytes, void* stream);
+/* TEST HOOK, host only (no device; ABI 129): the dispatch ssdk_postprocess would take for a call of this shape and these options, decided by
+ * the functions the real entry point launches by and under the environment of the call (SSDK_POST_SAMPLE / _NO_SAMPLE, SSDK_POST_WGS,
+ * SSDK_POST_NO_FOLD, SSDK_NMS_ONE_PASS, SSDK_POST_OLD).  sample: 1 / 0 = the plan with / without the sample pass where the shape allows
+ * one (the real call chooses by a hint the previous call left), < 0 = what the next call of this process would choose.  Refuses what
+ * ssdk_postprocess refuses on shape.  out[16]:
+ *   [0] pipeline: 0 = post_select2_kernel + post_nms_wave_kernel (+ post_finish_kernel or post_merge2_kernel), 1 = greedy
+ *       (max_per_class None or > 256: post_select_kernel + post_nms_any_kernel / post_softnms_any_kernel + post_merge_kernel),
+ *       2 = general (post_select_kernel + post_nms_kernel + post_merge_kernel)
+ *   [1] softmax  [4] 64-row tiles per image  [13] tie_up: the last mantissa bit of nms_threshold (pipeline 0 compares
+ *       inter with the midpoint of the threshold and the next float times the union; a tie goes up when the bit is set)
+ *   pipeline 0 only (0 otherwise): [2] pad, [3] JMAX of post_select2_kernel<SOFTMAX, PAD, JMAX>; [5] ns: sample tiles (0: no sample pass,
+ *   no post_tau_kernel); [6] Gs, [7] Ts, [8] Gm, [9] Tm: workgroups per image and tiles per workgroup of the sample / main pass;
+ *   [10] nseg; [11] list_cap: keys per (image, class) list; [12] khead: head size of the two-pass NMS (0: one pass,
+ *   post_nms_wave_kernel<.., 0>); [14] 1: head + post_finish_kernel, 0 with khead > 0: head, post_img_tau_kernel, tail and merge as
+ *   launches of their own; [15] reserved (0). */
+int ssdk_debug_postprocess_plan(int batch, int num_anchors, int num_classes, int softmax, int max_per_class, float nms_threshold,
+                                int soft_nms, int max_total, int sample, long long* out);
 
 /* ---- multi-scale heads (H1) ----------------------------------------------------------------------------------- */
 

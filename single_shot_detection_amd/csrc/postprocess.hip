@@ -1953,9 +1953,12 @@ static HotState* hot_state_for(hipStream_t s, int ncls, int khead, int K, int so
     return slot;
 }
 
-static bool post_wants_sample_pass(int K) {
+// `wanted` >= 0 stands in for the hint (ssdk_debug_postprocess_plan: the caller says which plan to describe); the environment still wins.
+static bool post_wants_sample_pass(int K, int wanted = -1) {
     if (getenv("SSDK_POST_NO_SAMPLE")) return false;
-    if (getenv("SSDK_POST_SAMPLE") || !g_post_hint) return true;
+    if (getenv("SSDK_POST_SAMPLE")) return true;
+    if (wanted >= 0) return wanted != 0;
+    if (!g_post_hint) return true;
     const unsigned v = *static_cast<volatile unsigned*>(g_post_hint);
     // nothing seen yet: the plan that is safe for long lists.  Crossover measured at batch 64, K = 100 (tools/bench_post.py bg<shift>):
     // 1 264 keys per list: 153 with / 168 us without the sample pass; 580: 130 / 117; 38: 96 / 77
@@ -2016,6 +2019,39 @@ static int nms_head_size(int ncls, int K, int max_total) {
     h = h < 16 ? 16 : h;
     if (h > kWave || 2 * h > K || (long long)ncls * h <= max_total || (long long)ncls * h > 256LL * kImgTauPer) return 0;
     return h;
+}
+
+// ---- the rest of the dispatch, as pure functions of the call's shape, options and environment: ssdk_postprocess / postprocess_v2 launch
+// by them and ssdk_debug_postprocess_plan reports them (no device is touched by any of them)
+enum { kPipeV2 = 0, kPipeGreedy = 1, kPipeGeneral = 2 };
+// max_per_class None (<= 0), or beyond the bit-matrix kernel: the greedy path
+static inline bool post_any_k(int max_per_class) { return max_per_class <= 0 || max_per_class > kMaxPerClass; }
+static inline int post_pipeline(const PostPlan& plan, int soft_nms, int max_per_class) {
+    if (plan.ok && !soft_nms && !post_any_k(max_per_class)) return kPipeV2;
+    return post_any_k(max_per_class) ? kPipeGreedy : kPipeGeneral;
+}
+// post_select2_kernel<.., PAD, JMAX>: a row of even length is padded by one float in LDS; four threads share a row, JMAX elements each
+static inline bool sel_pad(int num_classes) { return (num_classes & 1) == 0; }
+static inline int sel_jmax(int num_classes) {
+    const int jneed = cdiv(num_classes, 4);
+    return jneed <= 6 ? 6 : jneed <= 12 ? 12 : jneed <= 21 ? 21 : 24;
+}
+// the head size postprocess_v2 runs with (SSDK_NMS_STOP: debug, timing of the NMS stages alone, one pass)
+static inline int post_khead(int ncls, int K, int max_total) {
+    return (getenv("SSDK_NMS_STOP") && atoi(getenv("SSDK_NMS_STOP"))) ? 0 : nms_head_size(ncls, K, max_total);
+}
+// head + post_finish_kernel (bound, tail and merge in one launch) against the separate launches of SSDK_POST_NO_FOLD
+static inline bool post_folds_tail(int khead) { return khead && !getenv("SSDK_POST_NO_FOLD"); }
+// RN(inter / union) > thr  <=>  inter / union > (or >=) the midpoint of thr and the next float above it ...
+static inline double nms_thr_mid(float nms_threshold) {
+    const float thr_next = nextafterf(nms_threshold, INFINITY);
+    return 0.5 * ((double)nms_threshold + (double)thr_next);
+}
+// ... where a tie rounds to the even mantissa: up to thr_next when thr's is odd
+static inline int nms_tie_up(float nms_threshold) {
+    unsigned thr_bits;
+    memcpy(&thr_bits, &nms_threshold, 4);
+    return (int)(thr_bits & 1u);
 }
 
 static PostWs2 carve_post_ws2(void* ws, size_t npc, size_t K, const PostPlan& p, size_t* total) {
@@ -2081,7 +2117,7 @@ extern "C" size_t ssdk_postprocess_workspace_bytes_ex(int batch, int num_anchors
                                                       int max_total, int soft_nms) {
     if (batch <= 0 || num_anchors <= 0 || num_classes <= 0) return 0;
     const size_t ncls = (size_t)ncls_of(num_classes, softmax);
-    if (max_per_class <= 0 || max_per_class > kMaxPerClass) {   // None (<= 0) or beyond the bit-matrix kernel: the greedy path
+    if (post_any_k(max_per_class)) {   // the greedy path
         size_t t = 0;
         carve_post_any(nullptr, (size_t)batch, (size_t)num_anchors, ncls, (size_t)any_cap_of(num_anchors, max_per_class, max_total, soft_nms != 0), &t, soft_nms != 0);
         return t;
@@ -2106,24 +2142,24 @@ static int postprocess_v2(const PostPlan& p, const float* scores, const float* l
                           hipStream_t s) {
     const int ncls = ncls_of(num_classes, softmax), npc = batch * ncls;
     const PostWs2 w = carve_post_ws2(workspace, (size_t)npc, (size_t)max_per_class, p, nullptr);
-    const bool pad = (num_classes & 1) == 0;
+    const bool pad = sel_pad(num_classes);
     const int Cp = pad ? num_classes + 1 : num_classes;
     const size_t lds = (align_up((size_t)kPostTileRows * Cp, 4) + 5 * (size_t)ncls + 3 * kPostTileRows + kPostThreads / kWave) * 4 + (size_t)(kPostThreads / kWave) * kSelQueue * 2;
     SelArgs a;
     a.scores = scores; a.A = num_anchors; a.C = num_classes; a.ncls = ncls; a.c_off = softmax ? 1 : 0; a.thr = score_threshold;
     a.list_cap = p.list_cap; a.nseg = p.nseg; a.cand = w.cand; a.segcnt = w.segcnt; a.seghot = w.seghot; a.hotb = nullptr; a.hotb_per_image = 1;
     a.stop = getenv("SSDK_POST_STOP") ? atoi(getenv("SSDK_POST_STOP")) : 0;
-    const int jneed = cdiv(num_classes, 4);
-    const int khead_plan = (getenv("SSDK_NMS_STOP") && atoi(getenv("SSDK_NMS_STOP"))) ? 0 : nms_head_size(ncls, max_per_class, max_total);
+    const int jmax = sel_jmax(num_classes);
+    const int khead_plan = post_khead(ncls, max_per_class, max_total);
     auto launch = [&](int mode, int sel_tiles, int G, int T, int seg_off, int seg0, const unsigned* tau, const unsigned* hotb) -> int {
         a.mode = mode; a.sel_tiles = sel_tiles; a.tiles_per_wg = T; a.seg_off = seg_off; a.seg0 = seg0; a.tau = tau; a.hotb = hotb;
         const dim3 grid(G, batch), block(kPostThreads);
 #define SSDK_SEL(SM, PD, J) hipLaunchKernelGGL((post_select2_kernel<SM, PD, J>), grid, block, lds, s, a)
 #define SSDK_SEL_J(SM, PD)                          \
     do {                                            \
-        if (jneed <= 6) SSDK_SEL(SM, PD, 6);        \
-        else if (jneed <= 12) SSDK_SEL(SM, PD, 12); \
-        else if (jneed <= 21) SSDK_SEL(SM, PD, 21); \
+        if (jmax == 6) SSDK_SEL(SM, PD, 6);         \
+        else if (jmax == 12) SSDK_SEL(SM, PD, 12);  \
+        else if (jmax == 21) SSDK_SEL(SM, PD, 21);  \
         else SSDK_SEL(SM, PD, 24);                  \
     } while (0)
         if (softmax && pad) SSDK_SEL_J(true, true);
@@ -2157,12 +2193,8 @@ static int postprocess_v2(const PostPlan& p, const float* scores, const float* l
         if (rc) return rc;
     }
     if (a.stop > 0) return SSDK_OK;   // debug: timing of the select stages alone (outputs are not written)
-    // RN(inter / union) > thr  <=>  inter / union > (or >=) the midpoint of thr and the next float above it
-    const float thr_next = nextafterf(nms_threshold, INFINITY);
-    const double thr_mid = 0.5 * ((double)nms_threshold + (double)thr_next);
-    unsigned thr_bits;
-    memcpy(&thr_bits, &nms_threshold, 4);
-    const int tie_up = (int)(thr_bits & 1u);   // a tie rounds to the even mantissa: up to thr_next when thr's is odd
+    const double thr_mid = nms_thr_mid(nms_threshold);
+    const int tie_up = nms_tie_up(nms_threshold);
     NmsSrc src;
     src.cand = w.cand; src.list_cap = p.list_cap; src.seg_off = p.ns ? seg_off_main : 0; src.seg_cap = p.Tm * kPostTileRows;
     src.segcnt = w.segcnt; src.seghot = w.seghot; src.nseg_all = p.nseg; src.seg0 = p.Gs; src.nseg = p.Gm;
@@ -2170,12 +2202,12 @@ static int postprocess_v2(const PostPlan& p, const float* scores, const float* l
     unsigned* const hint = post_hint_word(s);
     src.nall_out = (hint && !p.ns) ? w.pc_nall : nullptr;   // (with a sample pass the estimate is the tau kernel's: the main pass' lists are pruned)
     const int nms_stop = getenv("SSDK_NMS_STOP") ? atoi(getenv("SSDK_NMS_STOP")) : 0;
-    const int khead = nms_stop ? 0 : nms_head_size(ncls, max_per_class, max_total);
+    const int khead = khead_plan;
 #define SSDK_NMS(TIE, MODE)                                                                                                                     \
     hipLaunchKernelGGL((post_nms_wave_kernel<TIE, MODE>), dim3(npc), dim3(kWave), 0, s, (const float4*)locs, (const float4*)priors, num_anchors, \
                        ncls, max_per_class, thr_mid, xy_scale, wh_scale, src, w.pc_rows, w.pc_score, w.pc_count, w.pc_m, nms_stop, khead,      \
                        w.img_tau, w.head_last, hot ? hot->acc : nullptr)
-    if (khead && !getenv("SSDK_POST_NO_FOLD")) {
+    if (post_folds_tail(khead)) {
         if (tie_up) SSDK_NMS(true, 1); else SSDK_NMS(false, 1);
         SSDK_CHECK_LAUNCH("post_nms_wave_kernel (head)");
         // the image's bound, the few classes to redo above it and the merge: one workgroup per image (post_finish_kernel)
@@ -2225,7 +2257,7 @@ extern "C" int ssdk_postprocess(const float* scores, const float* locs, const fl
                  "ssdk_postprocess: batch=%d anchors=%d classes=%d", batch, num_anchors, num_classes);
     SSDK_REQUIRE(scores && locs && priors && out && counts, SSDK_E_INVALID, "ssdk_postprocess: null pointer");
     SSDK_REQUIRE(((uintptr_t)locs & 15) == 0 && ((uintptr_t)priors & 15) == 0, SSDK_E_INVALID, "ssdk_postprocess: locs/priors must be 16-byte aligned");
-    const bool any_k = max_per_class <= 0 || max_per_class > kMaxPerClass;   // None, or beyond the bit-matrix kernel
+    const bool any_k = post_any_k(max_per_class);
     SSDK_REQUIRE(max_total <= kSortCap, SSDK_E_UNSUPPORTED, "ssdk_postprocess: max_total=%d > %d", max_total, kSortCap);
     SSDK_REQUIRE(!soft_nms || soft_sigma > 0.0f, SSDK_E_INVALID, "ssdk_postprocess: soft-NMS sigma must be > 0");
     const int ncls = ncls_of(num_classes, softmax);
@@ -2238,7 +2270,7 @@ extern "C" int ssdk_postprocess(const float* scores, const float* locs, const fl
     SSDK_REQUIRE((long long)batch * ncls < 2147483647LL && batch <= 65535, SSDK_E_INVALID, "ssdk_postprocess: grid too large");
     hipStream_t s = (hipStream_t)stream;
     const PostPlan plan = make_plan(batch, num_anchors, num_classes, softmax, max_per_class, max_total, post_wants_sample_pass(max_per_class));
-    if (plan.ok && !soft_nms && !any_k)
+    if (post_pipeline(plan, soft_nms, max_per_class) == kPipeV2)
         return postprocess_v2(plan, scores, locs, priors, batch, num_anchors, num_classes, softmax, score_threshold, max_per_class, nms_threshold,
                               max_total, xy_scale, wh_scale, out, out_cap, counts, nms_candidates, workspace, s);
     if (any_k) {
@@ -2296,5 +2328,26 @@ extern "C" int ssdk_postprocess(const float* scores, const float* locs, const fl
     hipLaunchKernelGGL(post_merge_kernel, dim3(batch), dim3(kPostThreads), sizeof(int) * (size_t)(ncls + 1), s, ncls, max_per_class,
                        max_total, w.pc_rows, w.pc_count, w.merge_keys, out, out_cap, counts);
     SSDK_CHECK_LAUNCH("post_merge_kernel");
+    return SSDK_OK;
+}
+
+// TEST HOOK, host only: the pipeline, instantiations and grid split ssdk_postprocess would take for a call of this shape and these options
+// under the environment of the call, from the functions the real entry point launches by.  Refuses what that entry point refuses on shape.
+extern "C" int ssdk_debug_postprocess_plan(int batch, int num_anchors, int num_classes, int softmax, int max_per_class, float nms_threshold,
+                                           int soft_nms, int max_total, int sample, long long* out) {
+    SSDK_REQUIRE(out, SSDK_E_INVALID, "ssdk_debug_postprocess_plan: null pointer");
+    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && num_classes > (softmax ? 1 : 0), SSDK_E_INVALID,
+                 "ssdk_debug_postprocess_plan: batch=%d anchors=%d classes=%d", batch, num_anchors, num_classes);
+    SSDK_REQUIRE(max_total <= kSortCap, SSDK_E_UNSUPPORTED, "ssdk_debug_postprocess_plan: max_total=%d > %d", max_total, kSortCap);
+    const int ncls = ncls_of(num_classes, softmax);
+    const PostPlan p = make_plan(batch, num_anchors, num_classes, softmax, max_per_class, max_total, post_wants_sample_pass(max_per_class, sample < 0 ? -1 : (sample != 0)));
+    const int pipe = post_pipeline(p, soft_nms, max_per_class);
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    out[0] = pipe; out[1] = softmax != 0; out[4] = p.tiles; out[13] = nms_tie_up(nms_threshold);
+    if (pipe != kPipeV2) return SSDK_OK;   // (one tile per workgroup trip, no sample pass, no head: the fields below stay 0)
+    const int khead = post_khead(ncls, max_per_class, max_total);
+    out[2] = sel_pad(num_classes); out[3] = sel_jmax(num_classes);
+    out[5] = p.ns; out[6] = p.Gs; out[7] = p.Ts; out[8] = p.Gm; out[9] = p.Tm; out[10] = p.nseg; out[11] = p.list_cap;
+    out[12] = khead; out[14] = post_folds_tail(khead);
     return SSDK_OK;
 }
