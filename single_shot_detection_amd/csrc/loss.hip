@@ -348,13 +348,19 @@ __device__ __forceinline__ float box_loss_grad(float a, float b, float beta) {
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// The focal modulating factor b^g (b = 1 - p_t in [0, 1], g >= 0) and its derivative g b^(g-1), as torch's pow and its backward define them where
+// a saturated probability gives b == 0: 0^0 = 1, and the derivative is 0 for g == 0 at every b and 1 for g == 1.  Raw __powf is
+// exp2(g * log2(b)): g * __powf(0, g - 1) is 0 * inf = NaN at g == 0, and 0^0 is whatever exp2(0 * -inf) happens to give.
+__device__ __forceinline__ float focal_pow(float b, float g) { return g == 0.0f ? 1.0f : __powf(b, g); }
+__device__ __forceinline__ float focal_dpow(float b, float g) { return g == 0.0f ? 0.0f : (g == 1.0f ? 1.0f : g * __powf(b, g - 1.0f)); }
+
 // bf/modules/losses.py:42-52 for one element; tg = one-hot target value
 __device__ __forceinline__ float focal_elem(float x, float tg, float gamma, float alpha) {
     const float aw = tg * alpha + (1.0f - tg) * (1.0f - alpha);
     float pb = sigmoid_f(x);
     pb = pb * tg + (1.0f - pb) * (1.0f - tg);
     const float ce = fmaxf(x, 0.0f) - x * tg + log1pf(__expf(-fabsf(x)));
-    return aw * __powf(1.0f - pb, gamma) * ce;
+    return aw * focal_pow(1.0f - pb, gamma) * ce;
 }
 __device__ __forceinline__ float focal_elem_grad(float x, float tg, float gamma, float alpha) {
     const float aw = tg * alpha + (1.0f - tg) * (1.0f - alpha);
@@ -363,7 +369,7 @@ __device__ __forceinline__ float focal_elem_grad(float x, float tg, float gamma,
     const float ce = fmaxf(x, 0.0f) - x * tg + log1pf(__expf(-fabsf(x)));
     const float om = 1.0f - pb;
     const float dpb = s * (1.0f - s) * (2.0f * tg - 1.0f);
-    return aw * (-gamma * __powf(om, gamma - 1.0f) * dpb * ce + __powf(om, gamma) * (s - tg));
+    return aw * (-focal_dpow(om, gamma) * dpb * ce + focal_pow(om, gamma) * (s - tg));
 }
 
 struct LossParams {
@@ -488,7 +494,7 @@ __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, co
                 } else if (p.cls_kind == SSDK_CLS_CROSS_ENTROPY) {
                     cls_acc += nlogpb;
                 } else {  // losses.py:56-78
-                    float l = __powf(1.0f - __expf(-nlogpb), p.gamma) * nlogpb;
+                    float l = focal_pow(1.0f - __expf(-nlogpb), p.gamma) * nlogpb;
                     if (p.alpha >= 0.0f) l *= (cls == 0 ? 1.0f - p.alpha : p.alpha);
                     cls_acc += l;
                 }
@@ -528,7 +534,7 @@ __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, co
                         val = l - x[cs];
                     } else if (p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL) {
                         const float nlogpb = l - x[cs];
-                        val = __powf(1.0f - __expf(-nlogpb), p.gamma) * nlogpb;
+                        val = focal_pow(1.0f - __expf(-nlogpb), p.gamma) * nlogpb;
                         if (p.alpha >= 0.0f) val *= (cs == 0 ? 1.0f - p.alpha : p.alpha);
                     } else {  // SSDK_CLS_CE_SOFT, losses.py:80-93 on the target of multibox_loss.py:68-71
                         const int pos_c = cs != -1 ? cs : -1;
@@ -713,7 +719,7 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
                 float coef = 1.0f;  // dL/dx_c = coef * (p_c - onehot_c)
                 if (p.cls_kind == SSDK_CLS_SOFTMAX_FOCAL) {
                     const float logpb = x[cls] - l, pb = __expf(logpb), om = 1.0f - pb;
-                    coef = -(p.gamma * __powf(om, p.gamma - 1.0f) * pb * logpb - __powf(om, p.gamma));
+                    coef = -(focal_dpow(om, p.gamma) * pb * logpb - focal_pow(om, p.gamma));
                     if (p.alpha >= 0.0f) coef *= (cls == 0 ? 1.0f - p.alpha : p.alpha);
                 }
                 for (int c = lane; c < p.C; c += kWave) o[c] = coef * (__expf(x[c] - l) - (c == cls ? 1.0f : 0.0f)) * g_cls;
