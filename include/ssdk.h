@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 129
+#define SSDK_VERSION 130
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -66,6 +66,17 @@ extern "C" {
 #define SSDK_LOC_MSE 3       /* torch.nn.MSELoss: d^2, gradient 2d (torch.nn.functional.mse_loss) */
 #define SSDK_LOC_HUBER 4     /* torch.nn.HuberLoss(delta = smooth_l1_beta): |d| < delta ? d^2 / 2 : delta (|d| - delta / 2),
                                 gradient d clamped to [-delta, delta] (torch.nn.functional.huber_loss) */
+/* IoU-based kinds on decoded corners, like SSDK_LOC_GIOU: P = the prediction's decoded corner box, T = the row's RAW target corners, and
+ * the target is left alone.  (5, 6 and 7 are no kinds: refused.)  iou = inter / uni exactly as SSDK_LOC_GIOU computes it, no epsilon;
+ * eps = 1e-7 only in the denominators these terms add.  cw = max(P.x2, T.x2) - min(P.x1, T.x1), ch likewise, c2 = cw^2 + ch^2 + eps;
+ * rho2 = the squared distance of the two centres; w, h of P and wg, hg of T are plain differences.  Gradients: max / min to the selected
+ * argument, half each at an exact tie, clamp(0) passes where its argument is >= 0 (torch autograd's rules, SSDK_LOC_GIOU's). */
+#define SSDK_LOC_IOU 8       /* IoULoss: 1 - iou */
+#define SSDK_LOC_DIOU 9      /* DistanceIoULoss (arXiv:1911.08287): 1 - iou + rho2 / c2 */
+#define SSDK_LOC_CIOU 10     /* CompleteIoULoss (same paper): DIoU + alpha v, v = 4 / pi^2 (atan(wg / hg) - atan(w / h))^2,
+                                alpha = v / (1 - iou + v + eps), a constant of the step: the gradient is alpha dv */
+#define SSDK_LOC_EIOU 11     /* EfficientIoULoss (arXiv:2101.08158, without the focal factor):
+                                DIoU + (w - wg)^2 / (cw^2 + eps) + (h - hg)^2 / (ch^2 + eps) */
 
 int ssdk_version(void);
 
@@ -92,6 +103,12 @@ int ssdk_box_to_centroids(const float* box, float* out, long long n, int inplace
 int ssdk_box_area(const float* box, float* out, long long n, void* stream);
 int ssdk_box_intersection(const float* a, int na, const float* b, int nb, int cartesian, int zero_incorrect, float* out, void* stream);
 int ssdk_box_iou(const float* a, int na, const float* b, int nb, int cartesian, int generalized, float* out, void* stream);
+/* The IoU-based box terms row by row (csrc/iou_loss.h: the arithmetic of the fused loss kernels, the same bits).  kind = SSDK_LOC_GIOU,
+ * _IOU, _DIOU, _CIOU or _EIOU (anything else: SSDK_E_INVALID); pred, target DEV [n,4] corner boxes, 16-byte aligned.
+ *   _fwd: out DEV [n] = the kind's value of row i.
+ *   _bwd: dpred DEV [n,4] (16-byte aligned) = grad_rows[i] * d value_i / d pred_i, grad_rows DEV [n].  No gradient towards target. */
+int ssdk_box_iou_loss_fwd(int kind, const float* pred, const float* target, long long n, float* out, void* stream);
+int ssdk_box_iou_loss_bwd(int kind, const float* pred, const float* target, const float* grad_rows, long long n, float* dpred, void* stream);
 size_t ssdk_nms_workspace_bytes(int n);
 int ssdk_nms(const float* boxes, const float* scores, int n, float overlap_threshold, float score_threshold, int max_per_class, int soft,
              float sigma, long long* picked, float* picked_boxes, float* picked_scores, int* count, void* workspace, size_t workspace_bytes,
@@ -330,7 +347,8 @@ typedef struct ssdk_loss_params {
  *   kinds), localisation: loc_kind over the positives.
  *   target DEV [batch, A, 6]: with SSDK_LOC_SMOOTH_L1 it is MUTATED like the reference -- columns 0..3 become the
  *          encoded regression targets (to_centroids + encode_box in place, multibox_loss.py:81-82 / box_coder.py:22-30),
- *          every anchor (the same for SSDK_LOC_L1 / _MSE / _HUBER); with SSDK_LOC_GIOU it is left alone (multibox_loss.py:77-79).
+ *          every anchor (the same for SSDK_LOC_L1 / _MSE / _HUBER); with SSDK_LOC_GIOU, _IOU, _DIOU, _CIOU and _EIOU it is left alone
+ *          (multibox_loss.py:77-79).
  *   out3   DEV float[3] = (loss, class_loss, loc_loss), each already divided by max(1, #positives).
  *   lse_valid != 0: the workspace already holds this batch's per-anchor log-sum-exp (left there by
  *          ssdk_hard_negative_mining on the same scores), so the scores are not read again for sampled negatives.

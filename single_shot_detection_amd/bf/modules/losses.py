@@ -13,6 +13,9 @@ the plain sums instead of MultiboxLoss's division by the positives.  Limits, eac
 ``ignore_index`` mapped onto the kernel's -1.  GeneralizedIoULoss (losses.py:109-114) is 1 - box_utils.generalized_iou on
 csrc/boxes.hip, forward only (no autograd: MultiboxLoss's GIoU term has its backward inside the fused kernel).
 
+IoULoss, DistanceIoULoss, CompleteIoULoss and EfficientIoULoss are not in the reference either: MultiboxLoss fuses them like
+GeneralizedIoULoss, and on their own they run box_utils.iou_loss (csrc/boxes.hip), which has a backward and 'none' (DESIGN.md §29).
+
 QualityFocalLoss and VarifocalLoss are not in the reference: the IoU-aware sigmoid losses that train on every anchor (sampler
 ``valid_sampler``), on the dense kernels of csrc/loss.hip; same surface, same limits.
 
@@ -217,6 +220,44 @@ class GeneralizedIoULoss(_Loss):  # losses.py:109-114
             raise NotImplementedError('GeneralizedIoULoss.forward on its own has no backward; inside MultiboxLoss it is fused (csrc/loss.hip)')
         loss = 1.0 - box_utils.generalized_iou(boxes, target, cartesian=False)
         return loss.mean() if self.reduction == 'mean' else loss.sum()
+
+
+class _IoUFamilyLoss(_Loss):
+    """The IoU-based box losses that are not in the reference.  Inside MultiboxLoss the term is fused into csrc/loss.hip (decoded corners
+    against the raw target, like GeneralizedIoULoss); on their own, ``forward(boxes, target)`` takes [Boxes, 4] corner boxes and runs
+    ``box_utils.iou_loss`` -- the same per-box arithmetic (csrc/iou_loss.h), with a backward towards ``boxes`` and all three reductions."""
+    IOU_LOSS = True
+    KIND = None
+
+    def __init__(self, reduction='mean'):   # (reduction by name, no **kwargs: MultiboxLoss's 'sum' survives filter_kwargs)
+        super(_IoUFamilyLoss, self).__init__(reduction=reduction)
+
+    def forward(self, boxes, target):
+        from ..utils import box_utils
+        loss = box_utils.iou_loss(boxes, target, self.KIND)
+        if self.reduction == 'none':
+            return loss
+        return loss.mean() if self.reduction == 'mean' else loss.sum()
+
+
+class IoULoss(_IoUFamilyLoss):
+    """1 - IoU."""
+    KIND = 'iou'
+
+
+class DistanceIoULoss(_IoUFamilyLoss):
+    """Distance-IoU loss (arXiv:1911.08287): 1 - IoU + rho^2 / c^2."""
+    KIND = 'diou'
+
+
+class CompleteIoULoss(_IoUFamilyLoss):
+    """Complete-IoU loss (arXiv:1911.08287): DIoU + alpha v; alpha is a constant of the step."""
+    KIND = 'ciou'
+
+
+class EfficientIoULoss(_IoUFamilyLoss):
+    """Efficient-IoU loss (arXiv:2101.08158, without the focal factor): DIoU + the width and height terms over the enclosing box's."""
+    KIND = 'eiou'
 
 
 class DistributionFocalLoss(_Loss):

@@ -5,7 +5,9 @@ GIoU into the loss, NMS into ``ssdk_postprocess``); they exist for callers of th
 ``matcher.match_per_prediction``.
 
 Inputs: CUDA tensors are used where they are; CPU tensors and numpy arrays (the reference's ``to_torch`` decorator, :8-15) are copied to
-the current CUDA device and the result comes back where the first argument lived.  There is no CPU implementation."""
+the current CUDA device and the result comes back where the first argument lived.  There is no CPU implementation.
+
+``iou_loss`` is not in the reference: the row-wise IoU, GIoU, DIoU, CIoU and EIoU box terms with autograd, CUDA tensors only."""
 import numpy as np
 import torch
 
@@ -123,6 +125,45 @@ def iou(a, b, cartesian=True):
 def generalized_iou(a, b, cartesian=True):
     """https://arxiv.org/pdf/1902.09630v2.pdf   (box_utils.py:104-143)"""
     return _iou(a, b, cartesian, 1, 'generalized_iou')
+
+
+IOU_LOSS_KINDS = {'giou': 1, 'iou': 8, 'diou': 9, 'ciou': 10, 'eiou': 11}   # SSDK_LOC_GIOU, _IOU, _DIOU, _CIOU, _EIOU (include/ssdk.h)
+
+
+class _IouLossFn(torch.autograd.Function):
+    """per-row values of ssdk_box_iou_loss_fwd; the backward is ssdk_box_iou_loss_bwd (no gradient towards the target)."""
+
+    @staticmethod
+    def forward(ctx, boxes, target, kind):
+        out = torch.empty((boxes.shape[0],), dtype=torch.float32, device=boxes.device)
+        _lib.check(_lib.lib().ssdk_box_iou_loss_fwd(kind, _lib.ptr(boxes), _lib.ptr(target), boxes.shape[0], _lib.ptr(out), _lib.current_stream()),
+                   'ssdk_box_iou_loss_fwd')
+        ctx.save_for_backward(boxes, target)
+        ctx.kind = kind
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        boxes, target = ctx.saved_tensors
+        g = grad.float().contiguous()
+        dboxes = torch.empty_like(boxes)
+        _lib.check(_lib.lib().ssdk_box_iou_loss_bwd(ctx.kind, _lib.ptr(boxes), _lib.ptr(target), _lib.ptr(g), boxes.shape[0], _lib.ptr(dboxes),
+                                                    _lib.current_stream()), 'ssdk_box_iou_loss_bwd')
+        return dboxes, None, None
+
+
+def iou_loss(boxes, target, kind):
+    """[Boxes, 4], [Boxes, 4] corners -> [Boxes]: the IoU-based box term of every row, ``kind`` in 'iou' | 'giou' | 'diou' | 'ciou' | 'eiou'
+    (1 - IoU, 1 - GIoU, arXiv:1911.08287's DIoU and CIoU, arXiv:2101.08158's EIoU without the focal factor; include/ssdk.h has the
+    formulas), with autograd towards ``boxes``: the per-box arithmetic of MultiboxLoss's fused box term (csrc/iou_loss.h).  CUDA tensors."""
+    if kind not in IOU_LOSS_KINDS:
+        raise ValueError(f'iou_loss: kind={kind!r}, expected one of {sorted(IOU_LOSS_KINDS)}')
+    if isinstance(boxes, np.ndarray) or isinstance(target, np.ndarray) or not boxes.is_cuda or not target.is_cuda:
+        raise RuntimeError('iou_loss runs on libssdk (HIP): CUDA tensors only')
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.shape != target.shape:
+        raise ValueError(f'iou_loss: boxes and target must both be [Boxes, 4], got {tuple(boxes.shape)} and {tuple(target.shape)}')
+    out = _IouLossFn.apply(boxes.float().contiguous(), target.detach().float().contiguous(), IOU_LOSS_KINDS[kind])
+    return out.to(boxes.dtype)
 
 
 def nms(boxes, scores, overlap_threshold, score_threshold, max_per_class=None, soft=False, sigma=0.5):

@@ -3,7 +3,10 @@
 // assign_kernel / gt_argmax_kernel (match.hip), GIoU inside loss_fwd (loss.hip), NMS inside the postprocess kernels -- but
 // matcher.match_per_prediction(weights, ...) takes an IoU matrix, and callers of the reference use the module directly.
 // Built -ffp-contract=off: every expression rounds op for op like the reference's separate torch ops (bit-exact against its goldens).
+#include <algorithm>
+
 #include "common.h"
+#include "iou_loss.h"
 
 namespace ssdk {
 
@@ -60,6 +63,25 @@ __global__ void __launch_bounds__(256) box_iou_kernel(const float4* __restrict__
     if (e >= total) return;
     const float4 A = a[cartesian ? e / nb : e], B = b[cartesian ? e % nb : e];
     out[e] = generalized ? giou_corner(A, B) : iou_corner(A, area4(A.x, A.y, A.z, A.w), B, area4(B.x, B.y, B.z, B.w));
+}
+
+// ---- the IoU-based box terms row by row (iou_loss.h: what the fused loss kernels of loss.hip compute per positive) ------------------------
+// One thread per box, grid-stride.  K: SSDK_LOC_GIOU, _IOU, _DIOU, _CIOU or _EIOU.
+constexpr int kIouLossMaxBlocks = 2048;
+template <int K>
+__global__ void __launch_bounds__(256) box_iou_loss_fwd_kernel(const float4* __restrict__ pred, const float4* __restrict__ target, long long n,
+                                                               float* __restrict__ out) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = corner_loss<K>(pred[i], target[i]);
+}
+template <int K>
+__global__ void __launch_bounds__(256) box_iou_loss_bwd_kernel(const float4* __restrict__ pred, const float4* __restrict__ target,
+                                                               const float* __restrict__ grad_rows, long long n, float4* __restrict__ dpred) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float4 d = corner_loss_grad<K>(pred[i], target[i]);
+        const float g = grad_rows[i];
+        dpred[i] = make_float4(g * d.x, g * d.y, g * d.z, g * d.w);
+    }
 }
 
 // ---- box_utils.py:166-194 nms for ONE problem (the batched, fused form is ssdk_postprocess) ------------------------------------------
@@ -253,6 +275,44 @@ extern "C" int ssdk_box_iou(const float* a, int na, const float* b, int nb, int 
     hipLaunchKernelGGL(box_iou_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, (const float4*)a, na, (const float4*)b, nb, cartesian, generalized,
                        out);
     SSDK_CHECK_LAUNCH("box_iou_kernel");
+    return SSDK_OK;
+}
+// index of an IoU kind in the two kernel tables below, -1 for anything else
+static int iou_loss_slot(int kind) {
+    if (kind == SSDK_LOC_GIOU) return 0;
+    return (kind >= SSDK_LOC_IOU && kind <= SSDK_LOC_EIOU) ? kind - SSDK_LOC_IOU + 1 : -1;
+}
+static int check_iou_loss(const char* fn, int kind, const float* pred, const float* target, long long n, const void* out) {
+    SSDK_REQUIRE(iou_loss_slot(kind) >= 0, SSDK_E_INVALID, "%s: kind=%d (SSDK_LOC_GIOU, _IOU, _DIOU, _CIOU or _EIOU)", fn, kind);
+    SSDK_REQUIRE(n >= 0 && (n == 0 || (pred && target && out)), SSDK_E_INVALID, "%s: n=%lld / null pointer", fn, n);
+    SSDK_REQUIRE((((uintptr_t)pred | (uintptr_t)target) & 15) == 0, SSDK_E_UNSUPPORTED, "%s: boxes must be 16-byte aligned", fn);
+    return SSDK_OK;
+}
+static inline unsigned iou_loss_blocks(long long n) { return (unsigned)std::min<long long>((n + 255) / 256, kIouLossMaxBlocks); }
+
+extern "C" int ssdk_box_iou_loss_fwd(int kind, const float* pred, const float* target, long long n, float* out, void* stream) {
+    int rc = check_iou_loss("ssdk_box_iou_loss_fwd", kind, pred, target, n, out);
+    if (rc) return rc;
+    if (!n) return SSDK_OK;
+    using Fn = decltype(&box_iou_loss_fwd_kernel<SSDK_LOC_GIOU>);
+    static const Fn k[5] = {box_iou_loss_fwd_kernel<SSDK_LOC_GIOU>, box_iou_loss_fwd_kernel<SSDK_LOC_IOU>, box_iou_loss_fwd_kernel<SSDK_LOC_DIOU>,
+                            box_iou_loss_fwd_kernel<SSDK_LOC_CIOU>, box_iou_loss_fwd_kernel<SSDK_LOC_EIOU>};
+    hipLaunchKernelGGL(k[iou_loss_slot(kind)], dim3(iou_loss_blocks(n)), dim3(256), 0, (hipStream_t)stream, (const float4*)pred, (const float4*)target, n, out);
+    SSDK_CHECK_LAUNCH("box_iou_loss_fwd_kernel");
+    return SSDK_OK;
+}
+extern "C" int ssdk_box_iou_loss_bwd(int kind, const float* pred, const float* target, const float* grad_rows, long long n, float* dpred, void* stream) {
+    int rc = check_iou_loss("ssdk_box_iou_loss_bwd", kind, pred, target, n, dpred);
+    if (rc) return rc;
+    SSDK_REQUIRE(n == 0 || grad_rows, SSDK_E_INVALID, "ssdk_box_iou_loss_bwd: null grad_rows");
+    SSDK_REQUIRE(((uintptr_t)dpred & 15) == 0, SSDK_E_UNSUPPORTED, "ssdk_box_iou_loss_bwd: dpred must be 16-byte aligned");
+    if (!n) return SSDK_OK;
+    using Fn = decltype(&box_iou_loss_bwd_kernel<SSDK_LOC_GIOU>);
+    static const Fn k[5] = {box_iou_loss_bwd_kernel<SSDK_LOC_GIOU>, box_iou_loss_bwd_kernel<SSDK_LOC_IOU>, box_iou_loss_bwd_kernel<SSDK_LOC_DIOU>,
+                            box_iou_loss_bwd_kernel<SSDK_LOC_CIOU>, box_iou_loss_bwd_kernel<SSDK_LOC_EIOU>};
+    hipLaunchKernelGGL(k[iou_loss_slot(kind)], dim3(iou_loss_blocks(n)), dim3(256), 0, (hipStream_t)stream, (const float4*)pred, (const float4*)target, grad_rows, n,
+                       (float4*)dpred);
+    SSDK_CHECK_LAUNCH("box_iou_loss_bwd_kernel");
     return SSDK_OK;
 }
 extern "C" size_t ssdk_nms_workspace_bytes(int n) {

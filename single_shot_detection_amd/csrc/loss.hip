@@ -13,7 +13,7 @@
 //                      instead of argsort(argsort()); ties at the threshold go to the lower anchor index.
 //   loss_fwd_kernel    one thread per anchor: target encode in place (to_centroids + encode_box, every anchor, as
 //                      the reference mutates it), the box term over positives (smooth-L1, L1, MSE or Huber on the encoded
-//                      target; GIoU on decoded corners), and the classification term for SAMPLED
+//                      target; GIoU, IoU, DIoU, CIoU and EIoU on decoded corners, iou_loss.h), and the classification term for SAMPLED
 //                      rows only (a gather of x[class] when the log-sum-exp is already there; otherwise the wave
 //                      cooperates on each sampled row).  Partial sums per workgroup, fixed-order final reduce.
 //   loss_bwd_kernel    64-row output tiles: zero-fill, fill the sampled rows, one coalesced write.
@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "iou_loss.h"
 
 namespace ssdk {
 
@@ -397,36 +398,7 @@ __device__ __forceinline__ float soft_t(int c, int pos, float s, int C, float ep
 // (decode_corners, the decoded corner box of a prediction, and box_quality, the plain IoU of the soft-target losses, live in common.h:
 // the task-aligned assigner of match.hip computes both)
 
-// 1 - generalized_iou (box_utils.py:104-143, cartesian=False) of predicted corners P against target corners T
-__device__ __forceinline__ float giou_loss(float4 P, float4 T) {
-    const float inter = area4(tmaxf(P.x, T.x), tmaxf(P.y, T.y), tminf(P.z, T.z), tminf(P.w, T.w));
-    const float uni = area4(P.x, P.y, P.z, P.w) + area4(T.x, T.y, T.z, T.w) - inter;
-    const float enc = area4(tminf(P.x, T.x), tminf(P.y, T.y), tmaxf(P.z, T.z), tmaxf(P.w, T.w));
-    return 1.0f - (inter / uni - (enc - uni) / enc);
-}
-
-// d(giou_loss)/dP: loss = 2 - inter/uni - uni/enc; max/min route the gradient to the selected argument (ties: half),
-// clamp(0) passes it where its argument is >= 0 (what autograd does for box_utils.py:104-143)
-__device__ __forceinline__ float4 giou_loss_grad(float4 P, float4 T) {
-    const float pw = P.z - P.x, ph = P.w - P.y, cw = clamp0(pw), ch = clamp0(ph);
-    const float area_p = cw * ch, area_t = area4(T.x, T.y, T.z, T.w);
-    const float ix1 = tmaxf(P.x, T.x), iy1 = tmaxf(P.y, T.y), ix2 = tminf(P.z, T.z), iy2 = tminf(P.w, T.w);
-    const float iw = clamp0(ix2 - ix1), ih = clamp0(iy2 - iy1), inter = iw * ih;
-    const float uni = area_p + area_t - inter;
-    const float ex1 = tminf(P.x, T.x), ey1 = tminf(P.y, T.y), ex2 = tmaxf(P.z, T.z), ey2 = tmaxf(P.w, T.w);
-    const float ew = clamp0(ex2 - ex1), eh = clamp0(ey2 - ey1), enc = ew * eh;
-    const float d_uni = inter / (uni * uni) - 1.0f / enc, d_enc = uni / (enc * enc);
-    const float c_inter = -1.0f / uni - d_uni, c_area = d_uni;
-    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto sel = [](float a, float b, bool greater) { return greater ? (a > b ? 1.0f : (a == b ? 0.5f : 0.0f)) : (a < b ? 1.0f : (a == b ? 0.5f : 0.0f)); };
-    if (pw >= 0.0f) { d.z += c_area * ch; d.x -= c_area * ch; }
-    if (ph >= 0.0f) { d.w += c_area * cw; d.y -= c_area * cw; }
-    if (ix2 - ix1 >= 0.0f) { const float g = c_inter * ih; d.z += g * sel(P.z, T.z, false); d.x -= g * sel(P.x, T.x, true); }
-    if (iy2 - iy1 >= 0.0f) { const float g = c_inter * iw; d.w += g * sel(P.w, T.w, false); d.y -= g * sel(P.y, T.y, true); }
-    if (ex2 - ex1 >= 0.0f) { const float g = d_enc * eh; d.z += g * sel(P.z, T.z, true); d.x -= g * sel(P.x, T.x, false); }
-    if (ey2 - ey1 >= 0.0f) { const float g = d_enc * ew; d.w += g * sel(P.w, T.w, true); d.y -= g * sel(P.y, T.y, false); }
-    return d;
-}
+// (giou_loss / giou_loss_grad and the IoU, DIoU, CIoU and EIoU terms live in iou_loss.h: the row-wise entry points of boxes.hip compute them too)
 
 // LK: the box-term kind.  CEX: SSDK_CLS_CROSS_ENTROPY with label smoothing and/or class weights -- its own instantiation, so the plain
 // kinds' code (the gather of x[class] off the sampler's log-sum-exp) and register allocation stay what they were.
@@ -459,10 +431,10 @@ __global__ void __launch_bounds__(kLossThreads) loss_fwd_kernel(LossParams p, co
             smp = sampled[r] != 0;
             npos += pos;
             const float4 pr = anchors[r % A];
-            if constexpr (LK == SSDK_LOC_GIOU) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
+            if constexpr (iou_kind(LK)) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
                 if (pos) {
                     float4 cen;
-                    loc_acc += giou_loss(decode_corners(locs[r], pr, p.xy_scale, p.wh_scale, cen), make_float4(t01.x, t01.y, t23.x, t23.y));
+                    loc_acc += corner_loss<LK>(decode_corners(locs[r], pr, p.xy_scale, p.wh_scale, cen), make_float4(t01.x, t01.y, t23.x, t23.y));
                 }
             } else {
             // box_utils.py:33-34 to_centroids(inplace), then box_coder.py:22-30 encode_box(inplace)
@@ -667,11 +639,11 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(LossParams p, in
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pos) {
                 const float4 l = locs[r];
-                if constexpr (LK == SSDK_LOC_GIOU) {
+                if constexpr (iou_kind(LK)) {
                     const float4 pr = anchors[r % A];
                     float4 cen;
                     const float4 P = decode_corners(l, pr, p.xy_scale, p.wh_scale, cen);
-                    const float4 d = giou_loss_grad(P, make_float4(t01.x, t01.y, t23.x, t23.y));
+                    const float4 d = corner_loss_grad<LK>(P, make_float4(t01.x, t01.y, t23.x, t23.y));
                     // corners = c -+ wh/2 ; c = p_xy + p_wh t / xy_scale ; wh = p_wh exp(t / wh_scale)
                     g = make_float4((d.x + d.z) * pr.z / p.xy_scale * g_loc, (d.y + d.w) * pr.w / p.xy_scale * g_loc,
                                     (d.z - d.x) * 0.5f * cen.z / p.wh_scale * g_loc, (d.w - d.y) * 0.5f * cen.w / p.wh_scale * g_loc);
@@ -830,14 +802,14 @@ __global__ void __launch_bounds__(kLossThreads) loss_dense_fwd_kernel(LossParams
             float q = 1.0f;
             float4 l = make_float4(0.f, 0.f, 0.f, 0.f), P = l;
             if (pos) l = locs[r];
-            if (pos && (LK == SSDK_LOC_GIOU || p.quality_from_iou)) {
+            if (pos && (iou_kind(LK) || p.quality_from_iou)) {
                 float4 cen;
                 P = decode_corners(l, pr, p.xy_scale, p.wh_scale, cen);
             }
             if (pos && p.quality_from_iou) q = box_quality(P, make_float4(t01.x, t01.y, t23.x, t23.y));   // the RAW corners: before the encode
             quality[r] = q;
-            if constexpr (LK == SSDK_LOC_GIOU) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
-                if (pos) loc_acc += giou_loss(P, make_float4(t01.x, t01.y, t23.x, t23.y));
+            if constexpr (iou_kind(LK)) {  // multibox_loss.py:77-79: decoded corners vs the RAW target, no mutation
+                if (pos) loc_acc += corner_loss<LK>(P, make_float4(t01.x, t01.y, t23.x, t23.y));
             } else {
                 // box_utils.py:33-34 to_centroids(inplace), then box_coder.py:22-30 encode_box(inplace) -- op for op loss_fwd_kernel's
                 t23.x -= t01.x; t23.y -= t01.y;
@@ -937,11 +909,11 @@ __global__ void __launch_bounds__(kLossThreads) loss_dense_bwd_kernel(LossParams
             float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pos) {
                 const float4 l = locs[r];
-                if constexpr (LK == SSDK_LOC_GIOU) {
+                if constexpr (iou_kind(LK)) {
                     const float4 pr = anchors[r % A];
                     float4 cen;
                     const float4 P = decode_corners(l, pr, p.xy_scale, p.wh_scale, cen);
-                    const float4 d = giou_loss_grad(P, make_float4(t01.x, t01.y, t23.x, t23.y));
+                    const float4 d = corner_loss_grad<LK>(P, make_float4(t01.x, t01.y, t23.x, t23.y));
                     // corners = c -+ wh/2 ; c = p_xy + p_wh t / xy_scale ; wh = p_wh exp(t / wh_scale)
                     g = make_float4((d.x + d.z) * pr.z / p.xy_scale * g_loc, (d.y + d.w) * pr.w / p.xy_scale * g_loc,
                                     (d.z - d.x) * 0.5f * cen.z / p.wh_scale * g_loc, (d.w - d.y) * 0.5f * cen.w / p.wh_scale * g_loc);
@@ -1102,10 +1074,19 @@ extern "C" int ssdk_valid_sampler(const float* target_classes, int class_stride,
     return SSDK_OK;
 }
 
+// Dense index of a box-term kind in the kernel tables: 0..4 are their own slot, SSDK_LOC_IOU .. _EIOU (8..11) follow; -1 for a value that
+// is no kind (5, 6 and 7 stay refused).
+constexpr int kLocSlots = 9;
+static int loc_slot(int kind) {
+    if (kind >= SSDK_LOC_SMOOTH_L1 && kind <= SSDK_LOC_HUBER) return kind;
+    if (kind >= SSDK_LOC_IOU && kind <= SSDK_LOC_EIOU) return kind - SSDK_LOC_IOU + SSDK_LOC_HUBER + 1;
+    return -1;
+}
+
 static int check_loss_params(const char* fn, const ssdk_loss_params* q) {
     SSDK_REQUIRE(q, SSDK_E_INVALID, "%s: null params", fn);
     SSDK_REQUIRE(q->cls_kind >= SSDK_CLS_CROSS_ENTROPY && q->cls_kind <= SSDK_CLS_VARIFOCAL, SSDK_E_INVALID, "%s: cls_kind=%d", fn, q->cls_kind);
-    SSDK_REQUIRE(q->loc_kind >= SSDK_LOC_SMOOTH_L1 && q->loc_kind <= SSDK_LOC_HUBER, SSDK_E_INVALID, "%s: loc_kind=%d", fn, q->loc_kind);
+    SSDK_REQUIRE(loc_slot(q->loc_kind) >= 0, SSDK_E_INVALID, "%s: loc_kind=%d", fn, q->loc_kind);
     SSDK_REQUIRE(q->loc_kind != SSDK_LOC_SMOOTH_L1 || q->smooth_l1_beta >= 0, SSDK_E_INVALID, "%s: SmoothL1 beta must be >= 0", fn);
     SSDK_REQUIRE(q->loc_kind != SSDK_LOC_HUBER || q->smooth_l1_beta > 0, SSDK_E_INVALID, "%s: Huber delta must be > 0", fn);
     SSDK_REQUIRE(q->ce_label_smoothing >= 0.0f && q->ce_label_smoothing <= 1.0f, SSDK_E_INVALID, "%s: ce_label_smoothing outside [0, 1]", fn);
@@ -1132,33 +1113,41 @@ static LossParams to_device_params(const ssdk_loss_params* q, int C, int lse_val
     return p;
 }
 
-// the loss kernels' instantiation for a box-term kind (LossParams::loc_kind after to_device_params, checked to be 0..4) and for plain /
+// the loss kernels' instantiation for a box-term kind (LossParams::loc_kind after to_device_params, checked by loc_slot) and for plain /
 // extended cross-entropy (label smoothing or class weights)
-static_assert(SSDK_LOC_SMOOTH_L1 == 0 && SSDK_LOC_GIOU == 1 && SSDK_LOC_L1 == 2 && SSDK_LOC_MSE == 3 && SSDK_LOC_HUBER == 4, "kernel tables");
 using LossFwdFn = decltype(&loss_fwd_kernel<SSDK_LOC_SMOOTH_L1, false>);
 using LossBwdFn = decltype(&loss_bwd_kernel<SSDK_LOC_SMOOTH_L1, false>);
+// (the tables' columns are loc_slot's: kinds 0..4, then 8..11)
+static_assert(SSDK_LOC_SMOOTH_L1 == 0 && SSDK_LOC_GIOU == 1 && SSDK_LOC_L1 == 2 && SSDK_LOC_MSE == 3 && SSDK_LOC_HUBER == 4 && SSDK_LOC_IOU == 8 &&
+              SSDK_LOC_DIOU == 9 && SSDK_LOC_CIOU == 10 && SSDK_LOC_EIOU == 11, "kernel tables");
 static bool ce_extended(const LossParams& p) { return p.cls_kind == SSDK_CLS_CROSS_ENTROPY && (p.ls != 0.0f || p.cw); }
 static LossFwdFn fwd_kernel_for(const LossParams& p) {
-    static const LossFwdFn k[2][5] = {
-        {loss_fwd_kernel<0, false>, loss_fwd_kernel<1, false>, loss_fwd_kernel<2, false>, loss_fwd_kernel<3, false>, loss_fwd_kernel<4, false>},
-        {loss_fwd_kernel<0, true>, loss_fwd_kernel<1, true>, loss_fwd_kernel<2, true>, loss_fwd_kernel<3, true>, loss_fwd_kernel<4, true>}};
-    return k[ce_extended(p)][p.loc_kind];
+    static const LossFwdFn k[2][kLocSlots] = {
+        {loss_fwd_kernel<0, false>, loss_fwd_kernel<1, false>, loss_fwd_kernel<2, false>, loss_fwd_kernel<3, false>, loss_fwd_kernel<4, false>,
+         loss_fwd_kernel<8, false>, loss_fwd_kernel<9, false>, loss_fwd_kernel<10, false>, loss_fwd_kernel<11, false>},
+        {loss_fwd_kernel<0, true>, loss_fwd_kernel<1, true>, loss_fwd_kernel<2, true>, loss_fwd_kernel<3, true>, loss_fwd_kernel<4, true>,
+         loss_fwd_kernel<8, true>, loss_fwd_kernel<9, true>, loss_fwd_kernel<10, true>, loss_fwd_kernel<11, true>}};
+    return k[ce_extended(p)][loc_slot(p.loc_kind)];
 }
 static LossBwdFn bwd_kernel_for(const LossParams& p) {
-    static const LossBwdFn k[2][5] = {
-        {loss_bwd_kernel<0, false>, loss_bwd_kernel<1, false>, loss_bwd_kernel<2, false>, loss_bwd_kernel<3, false>, loss_bwd_kernel<4, false>},
-        {loss_bwd_kernel<0, true>, loss_bwd_kernel<1, true>, loss_bwd_kernel<2, true>, loss_bwd_kernel<3, true>, loss_bwd_kernel<4, true>}};
-    return k[ce_extended(p)][p.loc_kind];
+    static const LossBwdFn k[2][kLocSlots] = {
+        {loss_bwd_kernel<0, false>, loss_bwd_kernel<1, false>, loss_bwd_kernel<2, false>, loss_bwd_kernel<3, false>, loss_bwd_kernel<4, false>,
+         loss_bwd_kernel<8, false>, loss_bwd_kernel<9, false>, loss_bwd_kernel<10, false>, loss_bwd_kernel<11, false>},
+        {loss_bwd_kernel<0, true>, loss_bwd_kernel<1, true>, loss_bwd_kernel<2, true>, loss_bwd_kernel<3, true>, loss_bwd_kernel<4, true>,
+         loss_bwd_kernel<8, true>, loss_bwd_kernel<9, true>, loss_bwd_kernel<10, true>, loss_bwd_kernel<11, true>}};
+    return k[ce_extended(p)][loc_slot(p.loc_kind)];
 }
 using DenseFwdFn = decltype(&loss_dense_fwd_kernel<SSDK_LOC_SMOOTH_L1>);
 using DenseBwdFn = decltype(&loss_dense_bwd_kernel<SSDK_LOC_SMOOTH_L1>);
 static DenseFwdFn dense_fwd_kernel_for(const LossParams& p) {
-    static const DenseFwdFn k[5] = {loss_dense_fwd_kernel<0>, loss_dense_fwd_kernel<1>, loss_dense_fwd_kernel<2>, loss_dense_fwd_kernel<3>, loss_dense_fwd_kernel<4>};
-    return k[p.loc_kind];
+    static const DenseFwdFn k[kLocSlots] = {loss_dense_fwd_kernel<0>, loss_dense_fwd_kernel<1>, loss_dense_fwd_kernel<2>, loss_dense_fwd_kernel<3>, loss_dense_fwd_kernel<4>,
+                                            loss_dense_fwd_kernel<8>, loss_dense_fwd_kernel<9>, loss_dense_fwd_kernel<10>, loss_dense_fwd_kernel<11>};
+    return k[loc_slot(p.loc_kind)];
 }
 static DenseBwdFn dense_bwd_kernel_for(const LossParams& p) {
-    static const DenseBwdFn k[5] = {loss_dense_bwd_kernel<0>, loss_dense_bwd_kernel<1>, loss_dense_bwd_kernel<2>, loss_dense_bwd_kernel<3>, loss_dense_bwd_kernel<4>};
-    return k[p.loc_kind];
+    static const DenseBwdFn k[kLocSlots] = {loss_dense_bwd_kernel<0>, loss_dense_bwd_kernel<1>, loss_dense_bwd_kernel<2>, loss_dense_bwd_kernel<3>, loss_dense_bwd_kernel<4>,
+                                            loss_dense_bwd_kernel<8>, loss_dense_bwd_kernel<9>, loss_dense_bwd_kernel<10>, loss_dense_bwd_kernel<11>};
+    return k[loc_slot(p.loc_kind)];
 }
 // The dense kernels' kinds: the two IoU-aware ones always, SigmoidFocalLoss only without a mask (with one it keeps the kernels it had).
 static bool dense_path(int cls_kind, const uint8_t* sampled) {

@@ -25,6 +25,10 @@ SSDK_LOC_GIOU = 1
 SSDK_LOC_L1 = 2
 SSDK_LOC_MSE = 3
 SSDK_LOC_HUBER = 4
+SSDK_LOC_IOU = 8
+SSDK_LOC_DIOU = 9
+SSDK_LOC_CIOU = 10
+SSDK_LOC_EIOU = 11
 
 
 _NO_ROW_HINT = bool(__import__('os').environ.get('SSDK_NO_ROW_HINT'))   # (measurement knob: the heads scan dscores as before round 4)
@@ -217,6 +221,14 @@ class MultiboxLoss(nn.Module):
                 raise ValueError(f'SmoothL1Loss: beta={self.smooth_l1_beta} must be >= 0')
         elif isinstance(ll, losses.GeneralizedIoULoss) and ll.reduction == 'sum':
             self.loc_kind = SSDK_LOC_GIOU
+        elif isinstance(ll, losses.IoULoss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_IOU
+        elif isinstance(ll, losses.DistanceIoULoss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_DIOU
+        elif isinstance(ll, losses.CompleteIoULoss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_CIOU
+        elif isinstance(ll, losses.EfficientIoULoss) and ll.reduction == 'sum':
+            self.loc_kind = SSDK_LOC_EIOU
         elif isinstance(ll, losses.L1Loss) and ll.reduction == 'sum':
             self.loc_kind = SSDK_LOC_L1
         elif isinstance(ll, losses.MSELoss) and ll.reduction == 'sum':
