@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 130
+#define SSDK_VERSION 131
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -903,6 +903,51 @@ int ssdk_mean_average_precision_ex(const float* predictions, long long n_pred, c
 size_t ssdk_sort_pairs_u64_workspace_bytes(long long n);
 int ssdk_sort_pairs_u64(const uint64_t* keys, const uint32_t* vals, long long n, int end_bit, uint64_t* keys_out, uint32_t* vals_out,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- COCO-style bbox evaluation: AP@[.50:.95], area bins, AR (ABI 131; not in the reference) --------------------------
+ * The published COCO rules (COCOeval.evaluateImg / accumulate / summarize), for boxes, on the device.
+ * Inputs.  predictions and ground truth as for ssdk_mean_average_precision; a non-zero column 6 (gt_stride > 6) marks a CROWD region
+ * (COCO's iscrowd, which is also its ignore).  gt_area DEV fp64 [total_gt] or NULL: the annotation's area (NULL: the box area).
+ * image_area_scale DEV fp64 [num_images] or NULL: multiplies every area of that image, gt (gt_area included) and detection, for the
+ * area-range test only (normalised boxes; NULL: 1).  Tables: iou_thrs DEV fp64 [T], rec_thrs DEV fp64 [R], area_rngs DEV fp64 [A][2]
+ * (lo, hi), max_dets HOST int32 [M], positive and strictly ascending (it sizes the walk, so the host must know it).
+ * Limits: T, A, M, R >= 1, T * A <= 64, M <= 4, R <= 1024, T * R * K * A * M < 2^31; anything else is refused with SSDK_E_INVALID, nothing launched.
+ * Arithmetic (evaluateImg / maskUtils.iou): fp64 from the fp32 coordinates, every operation rounded on its own.  area = (x2 - x1) * (y2 - y1);
+ * inter = max(0, min(x2) - max(x1)) * max(0, min(y2) - max(y1)); iou = inter / (area_d + area_g - inter), inter / area_d for a crowd gt,
+ * 0 for a zero denominator.
+ * Groups (evaluateImg): the detections of an (image, class) are ranked by (score descending, row ascending; -0.0 == +0.0); the first
+ * max_dets[M - 1] take part.  Per (threshold t, area range a): a gt is ignored when it is crowd or its area is < lo or > hi; gts are
+ * visited with the counted ones first, each part in row order; a detection in rank order takes the gt of the largest IoU >=
+ * min(t, 1 - 1e-10) (the last of equals), skipping gts already matched unless crowd, and never trading a counted match for an ignored
+ * gt; it inherits its gt's ignore flag; unmatched, it is ignored when its own area lies outside [lo, hi].
+ * Accumulation (accumulate): per (class k, a, max_dets m, t) the detections of rank < max_dets[m] in (score descending, image ascending,
+ * row ascending) order; tp = matched & ~ignored, fp = ~matched & ~ignored, cumulative; npig = class-k gts not ignored under a.  npig == 0:
+ * precision and recall are -1.  Otherwise rc = tp / npig, pr = tp / (fp + tp + 2^-52), recall = rc[last] (0 without detections), pr
+ * becomes its reverse running maximum, precision[t, r] = pr at the first position with rc >= rec_thrs[r], 0 when there is none.
+ * Outputs, all DEV fp64: precision [T, R, K, A, M], recall [T, K, A, M] (pycocotools' index order) and stats[12] (summarize) = AP, AP50,
+ * AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl: the mean of the entries > -1 of a slice, -1 without any.  All-area statistics
+ * take range 0, the s / m / l ones ranges 1 / 2 / 3; every AP and ARs / ARm / ARl take max_dets[M - 1], AR1 / AR10 / AR100 take max_dets[0] /
+ * [1] / [2]; a statistic whose index does not exist is -1; AP50 / AP75 take the threshold within 1e-9 of 0.5 / 0.75, -1 when absent.
+ * A detection of a class outside [0, num_classes) takes part in nothing; one of an image outside [0, num_images) has no ground truth.
+ * Every result is a function of the inputs alone: two runs give the same bits. */
+size_t ssdk_coco_eval_workspace_bytes(long long n_pred, long long total_gt, int num_classes, int num_iou_thrs, int num_area_rngs);
+int ssdk_coco_eval(const float* predictions, long long n_pred, const float* gt_rows, int gt_stride, const int* gt_offsets, int num_images,
+                   long long total_gt, int num_classes, const double* gt_area, const double* image_area_scale, const double* iou_thrs,
+                   int num_iou_thrs, const double* rec_thrs, int num_rec_thrs, const double* area_rngs, int num_area_rngs, const int* max_dets,
+                   int num_max_dets, double* precision, double* recall, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* The same call with the integer quantities behind the curves (each may be NULL; same workspace size):
+ *   rank_out  DEV int32 [n_pred] by prediction row: the position within its (image, class) group (evaluateImg's score order), -1 for a
+ *             foreign class.
+ *   flags_out DEV uint8 [n_pred, T * A] by prediction row, pair (t, a) at t * A + a: bit 0 = matched, bit 1 = ignored; 0 for a foreign class
+ *             and for rank >= max_dets[M - 1].
+ *   order_out DEV uint32 [n_pred]: prediction rows in (class ascending, score descending, image ascending, row ascending) order --
+ *             accumulate's order; foreign classes last, in (image, row) order.  Image ids order as signed integers.
+ *   npig_out  DEV int32 [K, A]. */
+int ssdk_coco_eval_ex(const float* predictions, long long n_pred, const float* gt_rows, int gt_stride, const int* gt_offsets, int num_images,
+                      long long total_gt, int num_classes, const double* gt_area, const double* image_area_scale, const double* iou_thrs,
+                      int num_iou_thrs, const double* rec_thrs, int num_rec_thrs, const double* area_rngs, int num_area_rngs, const int* max_dets,
+                      int num_max_dets, double* precision, double* recall, double* stats, int32_t* rank_out, uint8_t* flags_out,
+                      uint32_t* order_out, int32_t* npig_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- integral box head + Distribution Focal Loss (Generalized Focal Loss, arXiv:2006.04388; ABI 127; not in the reference) ----------
  *
