@@ -1,5 +1,6 @@
 """The float64 model of tests/conv_reference.py against torch.nn.functional.conv2d in float64 (forward and autograd), its weight
-re-layout against a plain loop, and the stated properties of int_pattern / assert_exact.  CPU only."""
+re-layout against a plain loop, the stated properties of int_pattern / assert_exact, the three-term (split-bf16) form of the model, and
+the conditions on the operands of every case of tests/test_conv_fast_exact_gpu.py.  CPU only."""
 import numpy as np
 import pytest
 import torch
@@ -205,3 +206,139 @@ def test_launch_plans_are_well_formed(count, direction):
             assert end == l.grid or 'streamk' in kernel, (specs, kernel, ranges, l.grid)
             in_order = [work[b] for b, _ in ranges]
             assert in_order == sorted(in_order, reverse=True), (specs, kernel, in_order)
+
+
+# ---- the three-term (split-bf16) model and the operands of tests/test_conv_fast_exact_gpu.py --------------------------------------------------
+
+def test_bf16_split_is_exact_with_two_integer_pieces_below_2_to_the_16():
+    v = np.arange(-(2 ** 16) + 1, 2 ** 16, dtype=np.int64)
+    h, m, rest = cr.bf16_split(v)
+    assert h.dtype == np.int64 and np.array_equal(h + m, v) and not rest.any()
+    pieces = lambda n: tuple(int(p[0]) for p in cr.bf16_split(np.array([n], np.int64)))
+    assert pieces(257) == (256, 1, 0) and pieces(259) == (260, -1, 0) and pieces(385) == (384, 1, 0) and pieces(514) == (512, 2, 0)
+    assert pieces(-259) == (-260, 1, 0) and pieces(3) == (3, 0, 0)
+    odd = v[(np.abs(v) >= 257) & (np.abs(v) <= 511) & (v % 2 != 0)]
+    assert (np.abs(cr.bf16_split(odd)[1]) == 1).all()
+    wide = v[(np.abs(v) >= 513) & (np.abs(v) <= 1023)]
+    assert np.abs(cr.bf16_split(wide)[1]).max() == 2
+    # rounding to nearest even against truncation: another h for a quarter of the integers in 257..511
+    r = np.arange(257, 512, dtype=np.int64)
+    assert abs(np.mean(cr.bf16_truncated(r) != cr.bf16_split(r)[0]) - 0.25) < 0.01
+
+
+def test_bf16_split_drops_a_third_piece_from_2_to_the_17():
+    """2^16 + 2^8 + 1 still has two pieces (bf16 steps by 512 there: it rounds UP to 66 048, and -255 fits a bf16); the smallest
+    integers with a third piece lie above 2^17, where the step is 1 024 -- the GPU tests' 2^17 + 2^8 + 1 is one."""
+    assert tuple(int(p[0]) for p in cr.bf16_split(np.array([65793], np.int64))) == (66048, -255, 0)
+    v = np.arange(-(2 ** 17), 2 ** 17 + 1, dtype=np.int64)
+    assert not cr.bf16_split(v)[2].any()
+    import test_conv_fast_exact_gpu as fast
+    assert fast.THIRD == 131329 and tuple(int(p[0]) for p in cr.bf16_split(np.array([fast.THIRD], np.int64))) == (131072, 256, 1)
+    assert tuple(int(p[0]) for p in cr.bf16_split(np.array([-fast.THIRD], np.int64))) == (-131072, -256, -1)
+
+
+def test_two_piece_pattern_has_mid_pieces_everywhere():
+    for lo, hi in ((257, 1023), (257, 511), (257, 287)):
+        a = cr.two_piece_pattern((3, 5, 7, 32), 4, lo, hi)
+        h, m, rest = cr.bf16_split(a)
+        assert np.abs(a).min() >= lo and np.abs(a).max() <= hi and (m != 0).all() and not rest.any()
+        assert 0.3 < np.mean(a > 0) < 0.7 and np.mean(cr.bf16_truncated(a) != h) > 0.2
+    s = cr.two_piece_pattern((3, 5, 7, 32), 4, density=0.1)
+    assert 0.05 < np.mean(s != 0) < 0.2
+
+
+@pytest.mark.parametrize('k,stride,pad', [(3, 1, 1), (3, 2, 1), (1, 1, 0), (3, 2, 0)])
+def test_three_term_model_is_the_sum_of_its_terms_and_the_exact_model_without_mid_pieces(k, stride, pad):
+    B, H, W, cin, cout = 2, 6, 5, 8, 4
+    ho, wo = cr.out_dim(H, k, stride, pad), cr.out_dim(W, k, stride, pad)
+    x, w, dy = cr.two_piece_pattern((B, H, W, cin), 1), cr.two_piece_pattern((cout, k, k, cin), 2), cr.two_piece_pattern((B, ho, wo, cout), 3)
+    bias = cr.int_pattern((cout,), -2, 2, 3)
+    (hx, mx, _), (hw_, mw, _), (hy, my, _) = cr.bf16_split(x), cr.bf16_split(w), cr.bf16_split(dy)
+    # sum(a b) - sum(m_a m_b), GEMM by GEMM
+    y3 = cr.conv_fwd(x, w, bias, stride, pad, 0, 'split3')
+    assert np.array_equal(y3, cr.conv_fwd(x, w, bias, stride, pad) - cr.conv_fwd(mx, mw, None, stride, pad))
+    assert not np.array_equal(y3, cr.conv_fwd(x, w, bias, stride, pad))
+    assert np.array_equal(cr.conv_fwd(x, w, bias, stride, pad, 1, 'split3'), np.maximum(y3, 0))
+    dx3, dw3, db3 = cr.conv_bwd(x, w, dy, stride, pad, ('split3', 'split3'))
+    dx, dw, db = cr.conv_bwd(x, w, dy, stride, pad)
+    assert np.array_equal(dx3, dx - cr.conv_bwd(x, mw, my, stride, pad)[0]) and np.array_equal(dw3, dw - cr.conv_bwd(mx, w, my, stride, pad)[1])
+    assert np.array_equal(db3, db)
+    mixed = cr.conv_bwd(x, w, dy, stride, pad, ('exact', 'split3'))
+    assert np.array_equal(mixed[0], dx) and np.array_equal(mixed[1], dw3)
+    # every m forced to 0 (operands that are their own h): the existing exact model
+    assert np.array_equal(cr.conv_fwd(hx, hw_, bias, stride, pad, 0, 'split3'), cr.conv_fwd(hx, hw_, bias, stride, pad))
+    for a, b in zip(cr.conv_bwd(hx, hw_, hy, stride, pad, ('split3', 'split3')), cr.conv_bwd(hx, hw_, hy, stride, pad)):
+        assert np.array_equal(a, b)
+    # the magnitudes bound every term group
+    assert (cr.conv_fwd(x, w, bias, stride, pad, 0, 'split3', mag=True) >= np.abs(y3)).all()
+    assert cr.assert_exact_model([np.array([5.0, 2 ** 24 - 2]), None], extra=1) == 2 ** 24 - 1
+    with pytest.raises(AssertionError):
+        cr.assert_exact_model(np.array([2.0 ** 24 - 1]), extra=1)
+
+
+def test_three_term_heads_model_takes_an_arithmetic_per_level_and_equals_the_exact_one_without_mid_pieces():
+    import test_conv_fast_exact_gpu as fast
+    defs, B = fast.HEADS_BWD['two']
+    one = fast.heads_backward_case(defs, B, 'a2', 1.0, ('split3', 'split3'))   # dy two-piece, x and w one-piece: equal to the exact model
+    for g, e in zip(one['grads'], one['grads_exact']):
+        assert all(np.array_equal(g[k], e[k]) for k in g)
+    P = fast.heads_backward_case(defs, B, 'both', 1.0, ('exact', 'split3'))
+    ds, dl = np.nan_to_num(P['ds']), np.nan_to_num(P['dl'])
+    per_level = cr.heads_bwd(P['levels'], B, ds, dl, [('split3', 'exact'), ('exact', 'split3')])
+    assert np.array_equal(per_level[0]['dw_score'], P['grads_exact'][0]['dw_score']) and np.array_equal(per_level[1]['dx'], P['grads_exact'][1]['dx'])
+    assert np.array_equal(per_level[1]['dw_loc'], P['grads'][1]['dw_loc']) and not np.array_equal(per_level[0]['dx'], P['grads_exact'][0]['dx'])
+
+
+def _differing(a, b):
+    return float(np.mean(np.asarray(a) != np.asarray(b)))
+
+
+def _fast_case_ids():
+    import test_conv_fast_exact_gpu as fast
+    return fast.all_cases()
+
+
+def _fast_case_name(c):
+    word = lambda p: ('x'.join(str(v) for v in p[:8]) if hasattr(p, 'cin') else '+'.join(word(q) for q in p) if isinstance(p, tuple) else str(p))
+    return '-'.join(word(p) for p in c)
+
+
+@pytest.mark.parametrize('case', _fast_case_ids(), ids=_fast_case_name)
+def test_fast_exact_gpu_case_meets_the_conditions_on_its_operands(case):
+    """For every case of tests/test_conv_fast_exact_gpu.py: the magnitude bound is below 2^24 (asserted while the case is built); a2 / b2:
+    every non-zero of the two-piece operand has a mid piece (at least half are asked for) and at least a fifth an h that truncation gets
+    wrong; `both`: the three-term answer differs from the exact product on at least half of the elements of every output tensor that is
+    three-term (behind a fused ReLU: of the elements it lets through, and it must cut at least a fifth -- the negative sums); `third`: the
+    dropped piece shows in every such tensor."""
+    import test_conv_fast_exact_gpu as fast
+    kind, regime = case[0], case[3] if case[0].startswith('heads') else case[2]
+    P = fast.case_of(case)
+    assert 0 < P['bound'] < 2 ** 24
+    if kind == 'fwd':
+        two, pairs = (P['x'] if regime == 'a2' else P['w']), [(P['y'], P['y_exact'], 'split3')]
+    elif kind == 'bwd':
+        two = P['dy'] if regime == 'a2' else np.concatenate([P['w'].ravel(), P['x'].ravel()])
+        pairs = [(P['dx'], P['dx_exact'], P['arith'][0]), (P['dw'], P['dw_exact'], P['arith'][1])]
+    elif kind == 'heads_fwd':
+        two = np.concatenate([lv['x' if regime == 'a2' else 'w_score'].ravel() for lv in P['levels']])
+        pairs = [(P['scores'], P['scores_exact'], 'split3'), (P['locs'], P['locs_exact'], 'split3')]
+    else:
+        two = np.nan_to_num(P['ds']) if regime == 'a2' else np.concatenate([lv[k].ravel() for lv in P['levels'] for k in ('x', 'w_score')])
+        arith = case[5]
+        pairs = [(g[k], e[k], arith[0] if k == 'dx' else arith[1]) for g, e in zip(P['grads'], P['grads_exact']) for k in ('dx', 'dw_score', 'dw_loc')
+                 if g[k] is not None]
+    if regime in ('a2', 'b2'):
+        nz = two[two != 0]
+        h, m, rest = cr.bf16_split(nz)
+        assert nz.size and np.mean(m != 0) >= 0.5 and np.mean(cr.bf16_truncated(nz) != h) >= 0.2 and not rest.any()
+        assert all(np.array_equal(a, b) for a, b, _ in pairs)   # one side has no mid piece: sum(a b)
+    for got, exact, arith in pairs:
+        if arith == 'exact':
+            assert np.array_equal(got, exact)
+        elif regime == 'both' and kind == 'fwd' and case[1].relu:
+            through = (got > 0) | (exact > 0)
+            assert np.mean(~through) >= 0.2 and _differing(got[through], exact[through]) >= 0.5
+        elif regime == 'both':
+            assert _differing(got, exact) >= 0.5, _differing(got, exact)
+        elif regime == 'third':
+            assert _differing(got, exact) > 0
