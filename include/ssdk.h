@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 131
+#define SSDK_VERSION 132
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -282,6 +282,48 @@ int ssdk_encode_ground_truth_tal(const float* gt_rows, int gt_stride, const int3
                                  const float* anchors, int num_anchors, const float* scores, int num_columns, const float* locs,
                                  float xy_scale, float wh_scale, int topk, float alpha, float beta, float* target, int32_t* box_idx,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+#define SSDK_SIMOTA_MAX_TOPK 32
+size_t ssdk_encode_ground_truth_simota_workspace_bytes(int batch, int total_gt, int num_anchors, int n_levels);
+/*
+ * Target assignment by SimOTA (YOLOX, arXiv:2107.08430 section 2.4: OTA, arXiv:2103.14259, with the Sinkhorn iteration replaced by a dynamic
+ * top-k; ABI 132; the reference has no such assigner).  The number of positives of a box comes from the prediction itself.  gt_rows,
+ * gt_stride, gt_offsets, batch, total_gt, anchors, scores, num_columns, locs, xy_scale, wh_scale, target, box_idx as for
+ * ssdk_encode_ground_truth_tal; level_sizes as for ssdk_encode_ground_truth_atss; beside them
+ *   level_strides   HOST float [n_levels * 2]: (sx, sy) per level, image pixels per cell of that level's map, finite and > 0.  Read during
+ *                   the call and handed to the kernels by value, so the call may sit in a captured HIP graph.  n_levels 1..SSDK_ATSS_MAX_LEVELS.
+ *   center_radius   finite, > 0 (YOLOX: 2.5); candidate_topk (q) 1..SSDK_SIMOTA_MAX_TOPK (YOLOX: 10); iou_weight finite, >= 0 (YOLOX: 3)
+ *   dynamic_k       DEV int32 [total_gt] or NULL: rule 5's k_g (0 in the padding rows past gt_offsets[batch])
+ * For every box g = (x1, y1, x2, y2, class, score) of an image and every anchor a = (cx, cy, w, h) of level l, all arithmetic in fp32, one
+ * operation at a time, nothing contracted:
+ *   1. P_a and u(a, g) are rules 1 and 2 of ssdk_encode_ground_truth_tal, by the same device functions.
+ *   2. Regions.  in_box: x1 < cx < x2 and y1 < cy < y2.  in_centre: with gcx = (x1 + x2) * 0.5f, gcy = (y1 + y2) * 0.5f,
+ *      rx = center_radius * sx_l, ry = center_radius * sy_l:  gcx - rx < cx < gcx + rx and gcy - ry < cy < gcy + ry.  NaN is in neither.
+ *      region = in_box || in_centre; penalised = !(in_box && in_centre).
+ *   3. Class term.  YOLOX's binary cross-entropy of the sigmoid row against the box's one-hot row, summed over the columns, is
+ *      S_a - x[a, k - 1] with S_a = sum_c softplus(x[a, c]), softplus(x) = fmaxf(x, 0) + __logf(1 + __expf(-|x|)), summed in fp32 in one
+ *      fixed order and computed once per call: eight partial sums, partial l over the column quads 4j..4j+3 with j = l, l + 8, ... in
+ *      ascending column order, then p[l] += p[l ^ 4], p[l] += p[l ^ 2], p[l] += p[l ^ 1].  k = (int)class.  A class outside
+ *      1..num_columns (NaN included) has the all-zero row: cls = S_a.  (There is no objectness branch: the probability is the class
+ *      sigmoid alone.)
+ *   4. cost(a, g) = cls + iou_weight * (-__logf(u + 1e-8f)).  A NaN cost ranks above every number.
+ *   5. n_g = the number of region anchors of g, q' = min(q, n_g); k_g = min(max((int)S, 1), q') with S the fp64 sum of the q' largest u
+ *      over the region anchors, largest first; k_g = 0 when n_g = 0.
+ *   6. The candidates of g are its k_g region anchors that are smallest by (penalised, cost, anchor index).  (The lexicographic order is
+ *      YOLOX's cost + 1e5 * penalised wherever the unpenalised cost is below 1e5, without the rounding of adding 1e5 in fp32.)
+ *   7. An anchor that is a candidate of several boxes goes to the smallest (penalised, cost), then the lowest box index.
+ *   8. box_idx[a] = g and the target row is the box's six columns (column 5 is the box's score, as ATSS; QualityFocalLoss(use_iou=True)
+ *      forms YOLOX's IoU-aware class target from it); every other anchor: SSDK_NOT_MATCHED and (0, 0, 0, 0, 0, 1).  No ignore band and no
+ *      force stage.
+ * One stated deviation from YOLOX / mmdet: a box ranks only anchors of its OWN region (YOLOX ranks the union of all boxes' regions, which
+ * differs only for a box with fewer than k_g region anchors: it would then take 1e5-penalised anchors from other boxes' regions).
+ * Three launches, nothing [G, A]- or [G, A, C]-shaped, no atomics, no host synchronisation, the same bits run to run.
+ */
+int ssdk_encode_ground_truth_simota(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                    const float* anchors, int num_anchors, const int32_t* level_sizes, const float* level_strides, int n_levels,
+                                    const float* scores, int num_columns, const float* locs, float xy_scale, float wh_scale,
+                                    float center_radius, int candidate_topk, float iou_weight, float* target, int32_t* box_idx,
+                                    int32_t* dynamic_k, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- sampler + loss (S1 + L1 + L2 + L3) ----------------------------------------------------------------------- */
 

@@ -23,6 +23,9 @@
 // And ssdk_encode_ground_truth_tal (not in the reference either): Task Alignment Learning, three launches of its own -- tal_candidates_kernel (one
 // workgroup per box: the topk inside anchors of largest s^alpha * u^beta, from the anchors' own predictions), tal_assign_kernel and
 // tal_normalise_kernel (one wave per box: column 5 of the rows the box kept); see further down.
+// And ssdk_encode_ground_truth_simota (not in the reference either): SimOTA, three launches of its own -- simota_class_sum_kernel (per region
+// anchor the softplus sum of its logits, the class cost's per-anchor part), simota_candidates_kernel (one workgroup per box: the count k_g
+// from its largest IoUs, then its k_g cheapest region anchors as a cutoff key) and simota_assign_kernel; see further down.
 // IoU is computed op for op like the reference (this TU is built -ffp-contract=off, IEEE divide) so that
 // assignments are bit-exact.
 #include "common.h"
@@ -769,6 +772,344 @@ __global__ void __launch_bounds__(kTalNormThreads) tal_normalise_kernel(const fl
     target[((size_t)i * A + a) * 6 + 5] = gt_rows[(size_t)g * gt_stride + 5] * t;
 }
 
+// ---- SimOTA (YOLOX, arXiv:2107.08430 section 2.4; not in the reference) ----------------------------------------------------------------
+// Per box: its REGION is the anchors whose centre lies strictly inside the box or inside a square of center_radius cells of the anchor's
+// own level around the box centre; an anchor outside either of the two is `penalised`.  cost = class BCE + iou_weight * -log(u) from the
+// anchor's own prediction; the box gets k_g = clamp((int)(sum of its q largest u), 1, #region) positives -- the count itself is a
+// reduction -- and they are its k_g region anchors smallest by (penalised, cost, anchor); a candidate of several boxes goes to the
+// smallest (penalised, cost), then the lowest box index (include/ssdk.h has the rule operation by operation).  The class BCE of anchor a
+// against the one-hot row of class k is S_a - x[a, k - 1] with S_a = sum_c softplus(x[a, c]): a number per anchor and one logit per
+// (anchor, box), so nothing [G, A, C]-shaped is ever read.  Three launches, no atomics, nothing zero-filled:
+//   1. simota_class_sum_kernel   one thread per (image, anchor) for the region test against the image's boxes from LDS; only the anchors in
+//                                some box's region have their C logits read -- eight lanes per row -- and S_a stored in the workspace.
+//                                Launches 2 and 3 both READ that value (and only at region anchors), which is why their keys agree bit
+//                                for bit.
+//   2. simota_candidates_kernel  one workgroup per box: ONE sweep of the anchor table, the region test first; a region anchor loads its loc,
+//                                S_a and the one logit of the box's class and becomes two keys -- (ord(u) << 32 | ~a), larger = better,
+//                                and (penalised << 63 | ord(cost) << 31 | a), smaller = better.  Up to q pops of the largest u-key give
+//                                the fp64 sum and k_g, then k_g pops of the smallest cost-key give the box's cutoff key.
+//   3. simota_assign_kernel      one thread per (image, anchor), on the pattern of tal_assign_kernel: it recomputes its cost-key against
+//                                every box whose region holds it with the SAME device functions and is a candidate exactly when
+//                                key <= cutoff(box).
+// (No candidate list leaves launch 2: nothing after it would read one -- column 5 is the box's score, there is no normalise pass.)
+constexpr int kSimotaThreads = 1024;
+constexpr int kSimotaWaves = kSimotaThreads / kWave;
+constexpr unsigned long long kSimotaNoKey = ~0ull;   // above every cost-key (an anchor index is below 2^31 - 1)
+// by value: level l owns anchors [off[l], off[l + 1]) (the entries past n repeat the total) and has the centre square's half sides
+// (rx, ry) = center_radius * (sx, sy), one fp32 product each, formed on the host
+struct SimotaLevels { int n; int off[SSDK_ATSS_MAX_LEVELS + 1]; float rx[SSDK_ATSS_MAX_LEVELS]; float ry[SSDK_ATSS_MAX_LEVELS]; };
+struct SimotaParams { float xy_scale, wh_scale, iou_weight; int C; };
+
+// (rx, ry) of anchor a's level (constant indices: a by-value table indexed by a variable would be copied to scratch)
+__device__ __forceinline__ float2 simota_radius(const SimotaLevels& lv, int a) {
+    float2 r = make_float2(lv.rx[0], lv.ry[0]);
+#pragma unroll
+    for (int q = 1; q < SSDK_ATSS_MAX_LEVELS; ++q) {
+        if (q >= lv.n) break;   // (the same in every lane: a scalar branch past the levels that do not exist)
+        if (a >= lv.off[q]) r = make_float2(lv.rx[q], lv.ry[q]);
+    }
+    return r;
+}
+// rule 2 on the inputs: exact.  gc = atss_centre(gb), r = simota_radius(level of p)
+__device__ __forceinline__ bool simota_region(float4 gb, float2 gc, float4 p, float2 r, bool& penalised) {
+    const bool in_box = gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w;
+    const bool in_centre = gc.x - r.x < p.x && p.x < gc.x + r.x && gc.y - r.y < p.y && p.y < gc.y + r.y;
+    penalised = !(in_box && in_centre);
+    return in_box || in_centre;
+}
+__device__ __forceinline__ float simota_softplus(float x) { return fmaxf(x, 0.0f) + __logf(1.0f + __expf(-fabsf(x))); }
+// rules 3 and 4: S the anchor's class sum, x the logit of the box's class (has_class: the class is one of the columns), u rule 1's quality
+__device__ __forceinline__ float simota_cost(float S, float x, bool has_class, float u, float iou_weight) {
+    const float cls = has_class ? S - x : S;
+    return cls + iou_weight * (-__logf(u + 1e-8f));
+}
+// smaller = better: the unpenalised before the penalised, then the lower cost (NaN above every number), then the lower anchor
+__device__ __forceinline__ unsigned long long simota_key(bool penalised, float cost, int a) {
+    const unsigned hi = (cost != cost) ? 0xFFFFFFFFu : ord_f32(cost);
+    return ((unsigned long long)(penalised ? 1u : 0u) << 63) | ((unsigned long long)hi << 31) | (unsigned long long)(unsigned)a;
+}
+// Rule 3's S_a of one row of logits, by the kSimotaRowLanes lanes of a lane group: lane l adds the softplus terms of the column quads
+// 4j..4j+3 with j = l, l + 8, ... in ascending column order into one accumulator (a quad is one 16-byte load where the row allows it: the
+// same additions in the same order either way), then the eight partial sums meet in a butterfly (xor 4, 2, 1), which leaves the same bits
+// in every lane.
+constexpr int kSimotaRowLanes = 8;
+__device__ __forceinline__ float simota_class_sum_lane(const float* __restrict__ x, int C, int l) {
+    const bool vec = (((uintptr_t)x) & 15) == 0;
+    const int full = C >> 2;
+    float s = 0.0f;
+    for (int j = l; j * 4 < C; j += kSimotaRowLanes) {
+        if (vec && j < full) {
+            const float4 v = reinterpret_cast<const float4*>(x)[j];
+            s += simota_softplus(v.x);
+            s += simota_softplus(v.y);
+            s += simota_softplus(v.z);
+            s += simota_softplus(v.w);
+        } else {
+            for (int c = 4 * j; c < min(4 * j + 4, C); ++c) s += simota_softplus(x[c]);
+        }
+    }
+    return s;
+}
+
+__global__ void __launch_bounds__(kAssignThreads) simota_class_sum_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                          const float4* __restrict__ anchors, int A, SimotaLevels lv,
+                                                                          const float* __restrict__ scores, int C, float* __restrict__ class_sum) {
+    __shared__ float4 s_box[kGtChunk];
+    __shared__ float2 s_centre[kGtChunk];
+    __shared__ int s_rows[kAssignThreads];
+    __shared__ int s_cnt[kAssignThreads / kWave];
+    const int i = blockIdx.y;
+    const int a = blockIdx.x * kAssignThreads + threadIdx.x;
+    const int g0 = gt_off[i], G = gt_off[i + 1] - g0;
+    const bool live = a < A;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    float2 r = make_float2(0.f, 0.f);
+    if (live && G > 0) {
+        p = anchors[a];
+        r = simota_radius(lv, a);
+    }
+    bool hit = false;   // the anchor lies in some box's region
+    for (int base = 0; base < G; base += kGtChunk) {
+        const int n = min(kGtChunk, G - base);
+        __syncthreads();
+        if (threadIdx.x < n) {
+            const float* row = gt_rows + (size_t)(g0 + base + threadIdx.x) * gt_stride;
+            const float4 gb = make_float4(row[0], row[1], row[2], row[3]);
+            s_box[threadIdx.x] = gb;
+            s_centre[threadIdx.x] = atss_centre(gb);
+        }
+        __syncthreads();
+        if (live && !hit)
+            for (int k = 0; k < n; ++k) {
+                bool pen;
+                if (simota_region(s_box[k], s_centre[k], p, r, pen)) { hit = true; break; }
+            }
+    }
+    // The block's region anchors, in anchor order, into s_rows (ballot + popcount: no atomics); then eight lanes per row, so that a row of
+    // logits is read as whole 128-byte runs instead of one 16-byte piece per lane and row.
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const unsigned long long mask = __ballot(hit);
+    if (lane == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, rows = 0;
+#pragma unroll
+    for (int w = 0; w < kAssignThreads / kWave; ++w) {
+        const int c = s_cnt[w];
+        before += w < wave ? c : 0;
+        rows += c;
+    }
+    if (hit) s_rows[before + __popcll(mask & ((1ull << lane) - 1ull))] = a;
+    __syncthreads();
+    const int l = threadIdx.x & (kSimotaRowLanes - 1), group = threadIdx.x / kSimotaRowLanes;
+    for (int r0 = 0; r0 < rows; r0 += kAssignThreads / kSimotaRowLanes) {   // (the same trip count in every lane: the shuffles below are unconditional)
+        const int slot = r0 + group;
+        const bool on = slot < rows;
+        const size_t row = (size_t)i * A + (on ? s_rows[slot] : 0);
+        float v = on ? simota_class_sum_lane(scores + row * C, C, l) : 0.0f;
+#pragma unroll
+        for (int m = kSimotaRowLanes / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+        if (on && l == 0) class_sum[row] = v;
+    }
+}
+
+__global__ void __launch_bounds__(kSimotaThreads) simota_candidates_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                           int batch, const float4* __restrict__ anchors, int A, SimotaLevels lv,
+                                                                           const float* __restrict__ scores, const float4* __restrict__ locs,
+                                                                           const float* __restrict__ class_sum, SimotaParams sp, int topk,
+                                                                           unsigned long long* __restrict__ cutoff, int32_t* __restrict__ dynamic_k) {
+    __shared__ unsigned long long s_red[2][kSimotaWaves];
+    const int g = blockIdx.x;
+    if (g >= gt_off[batch]) {   // rows past the last image's are padding (a row buffer of fixed capacity)
+        if (dynamic_k && threadIdx.x == 0) dynamic_k[g] = 0;
+        return;
+    }
+    const int i = tal_image_of(gt_off, batch, g);
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const float* r = gt_rows + (size_t)g * gt_stride;
+    const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
+    const float2 gc = atss_centre(gb);
+    const int col = tal_class_column(r[4], sp.C);
+    const size_t row0 = (size_t)i * A;
+    // An anchor against the box in two steps, so that a sweep round can have the gathered loads of its four anchors in flight together:
+    // `fetch` is the region test and, for a region anchor, the loads of its loc, class sum and the one logit of the box's class; `finish`
+    // turns what was fetched into the two keys.
+    struct Fetched { float4 t; float x, S; bool in, pen; };
+    auto fetch = [&](int a, const float4& p, Fetched& f) {
+        f.in = simota_region(gb, gc, p, simota_radius(lv, a), f.pen);
+        if (f.in) {
+            f.t = locs[row0 + a];
+            f.x = col >= 0 ? scores[(row0 + a) * sp.C + col] : 0.0f;
+            f.S = class_sum[row0 + a];
+        }
+    };
+    auto finish = [&](int a, const float4& p, const Fetched& f, unsigned long long& ku, unsigned long long& kc) {
+        if (!f.in) return false;
+        float4 cen;
+        const float4 P = decode_corners(f.t, p, sp.xy_scale, sp.wh_scale, cen);
+        const float u = box_quality(P, gb);
+        ku = make_key(ord_f32(u), a);   // never 0: the low word is ~a >= 2^31
+        kc = simota_key(f.pen, simota_cost(f.S, f.x, col >= 0, u, sp.iou_weight), a);
+        return true;
+    };
+    auto keys = [&](int a, const float4& p, unsigned long long& ku, unsigned long long& kc) {
+        Fetched f;
+        fetch(a, p, f);
+        return finish(a, p, f, ku, kc);
+    };
+    // The sweep: the thread's two largest u-keys (0 = none) and two smallest cost-keys (kSimotaNoKey = none) stay in registers (selects,
+    // as in atss_candidates_kernel).
+    unsigned long long u1 = 0ull, u2 = 0ull, c1 = kSimotaNoKey, c2 = kSimotaNoKey;
+    auto keep = [&](unsigned long long ku, unsigned long long kc) {
+        const bool gt1 = ku > u1, gt2 = ku > u2;
+        u2 = gt1 ? u1 : (gt2 ? ku : u2);
+        u1 = gt1 ? ku : u1;
+        const bool lt1 = kc < c1, lt2 = kc < c2;
+        c2 = lt1 ? c1 : (lt2 ? kc : c2);
+        c1 = lt1 ? kc : c1;
+    };
+    auto take = [&](int a, const float4& p, const Fetched& f) {
+        unsigned long long ku = 0ull, kc = kSimotaNoKey;
+        finish(a, p, f, ku, kc);
+        keep(ku, kc);
+    };
+    int a = threadIdx.x;
+    for (; a + 3 * kSimotaThreads < A; a += 4 * kSimotaThreads) {   // four anchor loads in flight, then the four anchors' gathered loads
+        const float4 p0 = anchors[a], p1 = anchors[a + kSimotaThreads], p2 = anchors[a + 2 * kSimotaThreads], p3 = anchors[a + 3 * kSimotaThreads];
+        Fetched f0, f1, f2, f3;
+        fetch(a, p0, f0);
+        fetch(a + kSimotaThreads, p1, f1);
+        fetch(a + 2 * kSimotaThreads, p2, f2);
+        fetch(a + 3 * kSimotaThreads, p3, f3);
+        take(a, p0, f0);
+        take(a + kSimotaThreads, p1, f1);
+        take(a + 2 * kSimotaThreads, p2, f2);
+        take(a + 3 * kSimotaThreads, p3, f3);
+    }
+    for (; a < A; a += kSimotaThreads) {
+        const float4 p = anchors[a];
+        Fetched f;
+        fetch(a, p, f);
+        take(a, p, f);
+    }
+    // Rule 5: up to topk pops of the workgroup's largest remaining u-key, one barrier each (the two halves of s_red alternate over BOTH pop
+    // loops); the first empty pop ends them: the box has fewer region anchors than topk.  Every thread adds the popped u to its own copy of
+    // the sum, in rank order.  The owner of a popped key moves on to its second key; a thread that loses both re-reads its own anchors.
+    int step = 0, qq = 0;
+    double sum = 0.0;
+    unsigned long long cur = u1;
+    for (int j = 0; j < topk; ++j, ++step) {
+        const unsigned long long w = wave_allreduce(cur, OpMaxU64());
+        if (lane == 0) s_red[step & 1][wave] = w;
+        __syncthreads();
+        unsigned long long popped = s_red[step & 1][0];
+#pragma unroll
+        for (int q = 1; q < kSimotaWaves; ++q) { const unsigned long long t = s_red[step & 1][q]; popped = t > popped ? t : popped; }
+        if (popped == 0ull) { ++step; break; }   // (the same value in every thread)
+        ++qq;
+        sum += (double)__uint_as_float(key_hi(popped) & 0x7FFFFFFFu);   // u >= 0: ord_f32 set the sign bit, 0 is kOrdZero
+        if (cur == popped) {
+            if (cur == u1) cur = u2;
+            else {
+                cur = 0ull;
+                for (int b = threadIdx.x; b < A; b += kSimotaThreads) {
+                    unsigned long long ku, kc;
+                    if (keys(b, anchors[b], ku, kc) && ku < popped && ku > cur) cur = ku;
+                }
+            }
+        }
+    }
+    int kg = 0;
+    if (qq > 0) kg = min(max((int)sum, 1), qq);   // (sum <= 32)
+    // Rule 6: kg pops of the smallest remaining cost-key; the last is the box's cutoff.  kg <= #region: no pop is empty.
+    unsigned long long last = 0ull;   // below every key: a box without a region anchor has no candidate
+    cur = c1;
+    for (int j = 0; j < kg; ++j, ++step) {
+        const unsigned long long w = wave_allreduce(cur, OpMinU64());
+        if (lane == 0) s_red[step & 1][wave] = w;
+        __syncthreads();
+        unsigned long long popped = s_red[step & 1][0];
+#pragma unroll
+        for (int q = 1; q < kSimotaWaves; ++q) { const unsigned long long t = s_red[step & 1][q]; popped = t < popped ? t : popped; }
+        last = popped;
+        if (cur == popped) {
+            if (cur == c1) cur = c2;
+            else {
+                cur = kSimotaNoKey;
+                for (int b = threadIdx.x; b < A; b += kSimotaThreads) {
+                    unsigned long long ku, kc;
+                    if (keys(b, anchors[b], ku, kc) && kc > popped && kc < cur) cur = kc;
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        cutoff[g] = last;
+        if (dynamic_k) dynamic_k[g] = kg;
+    }
+}
+
+__global__ void __launch_bounds__(kAssignThreads) simota_assign_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
+                                                                       const float4* __restrict__ anchors, int A, SimotaLevels lv,
+                                                                       const float* __restrict__ scores, const float4* __restrict__ locs,
+                                                                       const float* __restrict__ class_sum, SimotaParams sp,
+                                                                       const unsigned long long* __restrict__ cutoff, float* __restrict__ target,
+                                                                       int32_t* __restrict__ box_idx) {
+    __shared__ float4 s_box[kGtChunk];
+    __shared__ float2 s_centre[kGtChunk];
+    __shared__ int s_col[kGtChunk];
+    __shared__ unsigned long long s_cut[kGtChunk];
+    __shared__ __attribute__((aligned(16))) float s_out[kAssignThreads * 6];
+
+    const int i = blockIdx.y;
+    const int a0 = blockIdx.x * kAssignThreads;
+    const int a = a0 + threadIdx.x;
+    const int g0 = gt_off[i], G = gt_off[i + 1] - g0;
+    const bool live = a < A;
+    const size_t row = (size_t)i * A + (live ? a : 0);
+
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), P = p;
+    float2 rad = make_float2(0.f, 0.f);
+    if (live && G > 0) {
+        float4 cen;
+        p = anchors[a];
+        rad = simota_radius(lv, a);
+        P = decode_corners(locs[row], p, sp.xy_scale, sp.wh_scale, cen);
+    }
+    float S = 0.0f;
+    bool have_S = false;   // (launch 1 stored S only where some box's region holds the anchor: read it on the first hit)
+    unsigned long long best = 0ull;
+    int bi = SSDK_NOT_MATCHED;
+    for (int base = 0; base < G; base += kGtChunk) {
+        const int n = min(kGtChunk, G - base);
+        __syncthreads();
+        if (threadIdx.x < n) {
+            const int g = g0 + base + threadIdx.x;
+            const float* r = gt_rows + (size_t)g * gt_stride;
+            const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
+            s_box[threadIdx.x] = gb;
+            s_centre[threadIdx.x] = atss_centre(gb);
+            s_col[threadIdx.x] = tal_class_column(r[4], sp.C);
+            s_cut[threadIdx.x] = cutoff[g];
+        }
+        __syncthreads();
+        if (live)
+            for (int k = 0; k < n; ++k) {
+                const float4 gb = s_box[k];
+                bool pen;
+                if (!simota_region(gb, s_centre[k], p, rad, pen)) continue;
+                if (!have_S) { S = class_sum[row]; have_S = true; }
+                const int col = s_col[k];
+                const float x = col >= 0 ? scores[row * sp.C + col] : 0.0f;
+                const float u = box_quality(P, gb);
+                const unsigned long long key = simota_key(pen, simota_cost(S, x, col >= 0, u, sp.iou_weight), a);
+                if (key > s_cut[k]) continue;                                           // not among the box's k_g
+                const unsigned long long rank = key >> 31;                              // rule 7: (penalised, cost) without the anchor
+                if (bi < 0 || rank < best) { best = rank; bi = base + k; }              // ascending k, strict <: the lowest box index keeps a tie
+            }
+    }
+    write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
+}
+
 }  // namespace ssdk
 
 using namespace ssdk;
@@ -1032,5 +1373,81 @@ extern "C" int ssdk_encode_ground_truth_tal(const float* gt_rows, int gt_stride,
                            gt_offsets, batch, num_anchors, cand_anchor, cand_m, cand_u, cand_kept, target);
         SSDK_CHECK_LAUNCH("tal_normalise_kernel");
     }
+    return SSDK_OK;
+}
+
+static inline size_t simota_rows(int batch, int num_anchors) { return (size_t)(batch > 0 ? batch : 1) * (size_t)(num_anchors > 0 ? num_anchors : 1); }
+
+extern "C" size_t ssdk_encode_ground_truth_simota_workspace_bytes(int batch, int total_gt, int num_anchors, int n_levels) {
+    (void)n_levels;   // (the level table travels by value)
+    Carver c(nullptr);
+    c.take<float>(simota_rows(batch, num_anchors));               // S_a, written at region anchors only
+    c.take<unsigned long long>(tal_slots(total_gt));              // the boxes' cutoff keys
+    return c.off;
+}
+
+extern "C" int ssdk_encode_ground_truth_simota(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                                               const float* anchors, int num_anchors, const int32_t* level_sizes, const float* level_strides,
+                                               int n_levels, const float* scores, int num_columns, const float* locs, float xy_scale,
+                                               float wh_scale, float center_radius, int candidate_topk, float iou_weight, float* target,
+                                               int32_t* box_idx, int32_t* dynamic_k, void* workspace, size_t workspace_bytes, void* stream) {
+    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_simota: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
+    SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: batch exceeds grid limits");
+    SSDK_REQUIRE(gt_offsets && anchors && target && level_sizes && level_strides && (gt_rows || total_gt == 0), SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_simota: null pointer");
+    SSDK_REQUIRE(scores && locs, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: null scores or locs (the rule reads the anchors' own predictions)");
+    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: gt_stride=%d < 6", gt_stride);
+    SSDK_REQUIRE(num_columns >= 1, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: num_columns=%d < 1", num_columns);
+    SSDK_REQUIRE(n_levels >= 1 && n_levels <= SSDK_ATSS_MAX_LEVELS, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: n_levels=%d outside 1..%d",
+                 n_levels, SSDK_ATSS_MAX_LEVELS);
+    SSDK_REQUIRE(candidate_topk >= 1 && candidate_topk <= SSDK_SIMOTA_MAX_TOPK, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_simota: candidate_topk=%d outside 1..%d", candidate_topk, SSDK_SIMOTA_MAX_TOPK);
+    SSDK_REQUIRE(center_radius > 0.0f && center_radius <= FLT_MAX, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_simota: center_radius=%g must be finite and positive", (double)center_radius);
+    SSDK_REQUIRE(iou_weight >= 0.0f && iou_weight <= FLT_MAX, SSDK_E_INVALID,
+                 "ssdk_encode_ground_truth_simota: iou_weight=%g must be finite and not negative", (double)iou_weight);
+    SimotaLevels lv;
+    lv.n = n_levels;
+    long long sum = 0;
+    for (int l = 0; l <= SSDK_ATSS_MAX_LEVELS; ++l) {
+        lv.off[l] = (int)sum;   // (the entries past n_levels repeat the total)
+        if (l < SSDK_ATSS_MAX_LEVELS) lv.rx[l] = lv.ry[l] = 0.0f;
+        if (l < n_levels) {
+            SSDK_REQUIRE(level_sizes[l] > 0, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: level_sizes[%d]=%d", l, level_sizes[l]);
+            sum += level_sizes[l];
+            SSDK_REQUIRE(sum <= num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: level sizes exceed the %d anchors", num_anchors);
+            const float sx = level_strides[2 * l], sy = level_strides[2 * l + 1];
+            SSDK_REQUIRE(sx > 0.0f && sx <= FLT_MAX && sy > 0.0f && sy <= FLT_MAX, SSDK_E_INVALID,
+                         "ssdk_encode_ground_truth_simota: level_strides[%d]=(%g, %g) must be finite and positive", l, (double)sx, (double)sy);
+            const volatile float rx = center_radius * sx, ry = center_radius * sy;   // rule 2: one fp32 product each
+            lv.rx[l] = rx;
+            lv.ry[l] = ry;
+        }
+    }
+    SSDK_REQUIRE(sum == num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: level sizes sum to %lld, not to the %d anchors", sum,
+                 num_anchors);
+    SSDK_REQUIRE((((uintptr_t)anchors | (uintptr_t)locs) & 15) == 0, SSDK_E_UNSUPPORTED,
+                 "ssdk_encode_ground_truth_simota: anchors and locs must be 16-byte aligned");
+    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_simota_workspace_bytes(batch, total_gt, num_anchors, n_levels),
+                 SSDK_E_WORKSPACE, "ssdk_encode_ground_truth_simota: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    Carver c(workspace);
+    float* class_sum = c.take<float>(simota_rows(batch, num_anchors));
+    unsigned long long* cutoff = c.take<unsigned long long>(tal_slots(total_gt));
+    SimotaParams sp;
+    sp.xy_scale = xy_scale; sp.wh_scale = wh_scale; sp.iou_weight = iou_weight; sp.C = num_columns;
+    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
+    if (total_gt > 0) {
+        hipLaunchKernelGGL(simota_class_sum_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
+                           num_anchors, lv, scores, num_columns, class_sum);
+        SSDK_CHECK_LAUNCH("simota_class_sum_kernel");
+        hipLaunchKernelGGL(simota_candidates_kernel, dim3(total_gt), dim3(kSimotaThreads), 0, s, gt_rows, gt_stride, gt_offsets, batch,
+                           (const float4*)anchors, num_anchors, lv, scores, (const float4*)locs, class_sum, sp, candidate_topk, cutoff, dynamic_k);
+        SSDK_CHECK_LAUNCH("simota_candidates_kernel");
+    }
+    hipLaunchKernelGGL(simota_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors, lv,
+                       scores, (const float4*)locs, class_sum, sp, cutoff, target, box_idx);
+    SSDK_CHECK_LAUNCH("simota_assign_kernel");
     return SSDK_OK;
 }

@@ -58,6 +58,7 @@ class Detector(nn.Module):
         self.priors = anchor_generators
         self._anchor_cache = {}
         self._anchor_levels = {}
+        self._anchor_strides = {}
 
     def generate_anchors(self, img, sources):
         key = (tuple(img.shape[2:]), tuple(tuple(s.shape[2:]) for s in sources), str(img.device))
@@ -65,6 +66,7 @@ class Detector(nn.Module):
             anchors = [g.generate(img, s).reshape(-1) for s, g in zip(sources, self.priors)]
             self._anchor_cache[key] = torch.cat(anchors, dim=0).view(-1, 4)
             self._anchor_levels[key] = tuple(a.numel() // 4 for a in anchors)
+            self._anchor_strides[key] = tuple((float(img.shape[3]) / float(s.shape[3]), float(img.shape[2]) / float(s.shape[2])) for s in sources)
         return self._anchor_cache[key]
 
     def anchor_level_sizes(self, anchors):
@@ -73,6 +75,14 @@ class Detector(nn.Module):
             if cached is anchors:
                 return self._anchor_levels[key]
         raise ValueError('anchor_level_sizes: not a tensor this detector generated')
+
+    def anchor_level_strides(self, anchors):
+        """``(sx, sy)`` of every pyramid level of a tensor ``generate_anchors`` handed out: image pixels per cell of the level's map, image
+        size / map size (what ``SimOtaAssigner`` needs beside ``anchor_level_sizes``)."""
+        for key, cached in self._anchor_cache.items():
+            if cached is anchors:
+                return self._anchor_strides[key]
+        raise ValueError('anchor_level_strides: not a tensor this detector generated')
 
     def forward(self, img):
         scores, locs, locs_sources = self.predictor.forward(img)

@@ -15,15 +15,17 @@ from .box_coder import BoxCoder, build_box_coder  # noqa: F401
 from .detector_wrapper import DetectorWrapper
 from .losses.multibox_loss import MultiboxLoss
 from .postprocessor import Postprocessor
-from .target_assigner import AtssTargetAssigner, TargetAssigner, TaskAlignedAssigner
+from .target_assigner import AtssTargetAssigner, SimOtaAssigner, TargetAssigner, TaskAlignedAssigner
 
-TARGET_ASSIGNERS = {'TargetAssigner': TargetAssigner, 'AtssTargetAssigner': AtssTargetAssigner, 'TaskAlignedAssigner': TaskAlignedAssigner}
+TARGET_ASSIGNERS = {'TargetAssigner': TargetAssigner, 'AtssTargetAssigner': AtssTargetAssigner, 'TaskAlignedAssigner': TaskAlignedAssigner,
+                    'SimOtaAssigner': SimOtaAssigner}
 
 
 def build_target_assigner(args):
     """A config's ``target_assigner`` dict.  ``'name'`` (not in the reference) picks the class, by default ``'TargetAssigner'``, whose
     keywords the other entries are: ``{'name': 'AtssTargetAssigner', 'topk': 9}`` is the adaptive assigner, ``{'name': 'TaskAlignedAssigner',
-    'topk': 13}`` the prediction-aware one (``step_fn`` hands it the step's own prediction and the box coder)."""
+    'topk': 13}`` the prediction-aware one (``step_fn`` hands it the step's own prediction and the box coder), ``{'name': 'SimOtaAssigner'}``
+    YOLOX's dynamic top-k (the prediction, the box coder and the detector's level sizes and strides)."""
     args = dict(args)
     name = args.pop('name', 'TargetAssigner')
     if name not in TARGET_ASSIGNERS:
@@ -77,6 +79,10 @@ def init(device, model_args, box_coder_args, postprocess_args, loss_args, sample
     detector_wrapper = DetectorWrapper(detector, preprocess, postprocessor)
 
     def encode_ground_truth(ground_truth, priors, prediction):
+        if isinstance(target_assigner, SimOtaAssigner):   # (the prediction, and a centre square measured in cells of the anchor's level)
+            return target_assigner.encode_ground_truth(ground_truth, priors, prediction, box_coder,
+                                                       level_sizes=detector.anchor_level_sizes(priors),
+                                                       level_strides=detector.anchor_level_strides(priors))
         if isinstance(target_assigner, TaskAlignedAssigner):   # (it ranks the anchors by their own prediction, a constant of the step)
             return target_assigner.encode_ground_truth(ground_truth, priors, prediction, box_coder)
         if isinstance(target_assigner, AtssTargetAssigner):   # (it selects per pyramid level)

@@ -4,7 +4,8 @@ reference's own function on a given weight matrix (``ssdk_match_per_prediction``
 ``match_bipartite`` (matcher.py:7-31) is the reference's own function on a given matrix too (``ssdk_match_bipartite``); nothing in the
 reference calls it, here it is also the opt-in force stage of the fused path (``TargetAssigner(force_match='bipartite')``).
 ``match_atss`` is the one-image form of ``AtssTargetAssigner`` (``ssdk_encode_ground_truth_atss``), which the reference does not have;
-``match_task_aligned`` that of ``TaskAlignedAssigner`` (``ssdk_encode_ground_truth_tal``), which it does not have either."""
+``match_task_aligned`` that of ``TaskAlignedAssigner`` (``ssdk_encode_ground_truth_tal``) and ``match_simota`` that of ``SimOtaAssigner``
+(``ssdk_encode_ground_truth_simota``), which it does not have either."""
 import torch
 
 from .. import _lib
@@ -106,4 +107,22 @@ def match_task_aligned(gt_boxes, gt_classes, anchors, scores, locs, box_coder, t
     gt[:, 5] = 1.0
     _, idx = TaskAlignedAssigner(topk, alpha, beta).encode_ground_truth([gt], anchors, (scores.reshape(1, -1), locs.reshape(1, -1)), box_coder,
                                                                          return_box_idx=True)
+    return idx[0].long()
+
+
+def match_simota(gt_boxes, gt_classes, anchors, scores, locs, box_coder, level_sizes, level_strides, center_radius=2.5, candidate_topk=10,
+                 iou_weight=3.0):
+    """box_idx int64 [A] for one image by SimOTA (``SimOtaAssigner``; not in the reference): the box an anchor is positive for, else
+    NOT_MATCHED -- there is no ignore band and no force stage.  ``gt_boxes`` [G, >=4] corner form, ``gt_classes`` [G] (1-based: class k is
+    column k - 1 of the logits), ``anchors`` [A, 4] centroid, ``scores`` [A, C] (or [A * C]) class logits and ``locs`` [A, 4] (or [A * 4])
+    encoded boxes of that image, ``box_coder`` the coder that decodes them, ``level_sizes`` the anchor count and ``level_strides`` the
+    ``(sx, sy)`` image pixels per cell of every pyramid level."""
+    from .target_assigner import SimOtaAssigner
+    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
+    gt[:, :4] = gt_boxes[:, :4]
+    gt[:, 4] = gt_classes.to(gt.device).reshape(-1).float()
+    gt[:, 5] = 1.0
+    _, idx = SimOtaAssigner(center_radius, candidate_topk, iou_weight).encode_ground_truth(
+        [gt], anchors, (scores.reshape(1, -1), locs.reshape(1, -1)), box_coder, level_sizes=level_sizes, level_strides=level_strides,
+        return_box_idx=True)
     return idx[0].long()

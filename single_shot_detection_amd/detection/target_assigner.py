@@ -1,5 +1,6 @@
 """TargetAssigner -- mirror of detection/target_assigner.py:17-63 on libssdk (csrc/match.hip); AtssTargetAssigner, the adaptive assigner
-the reference does not have, beside it; and TaskAlignedAssigner, the prediction-aware one of TOOD, which it does not have either."""
+the reference does not have, beside it; TaskAlignedAssigner, the prediction-aware one of TOOD, and SimOtaAssigner, the dynamic top-k of
+YOLOX, which it does not have either."""
 import ctypes
 
 import numpy as np
@@ -269,3 +270,106 @@ class TaskAlignedAssigner(object):
         # keep the staging tensors alive until the stream has consumed them
         target._ssdk_keepalive = (rows, offs, scores, locs)
         return (target, box_idx) if return_box_idx else target
+
+
+SIMOTA_MAX_TOPK = 32   # SSDK_SIMOTA_MAX_TOPK (include/ssdk.h)
+SIMOTA_MAX_LEVELS = 16   # SSDK_ATSS_MAX_LEVELS
+
+
+class SimOtaAssigner(object):
+    """SimOTA (YOLOX, arXiv:2107.08430 section 2.4: OTA with the Sinkhorn iteration replaced by a dynamic top-k; not in the reference):
+    the assigner that decides HOW MANY positives a box gets from the prediction itself.  A box's region is the anchors whose centre lies
+    strictly inside it or inside a square of ``center_radius`` cells of the anchor's own level around the box centre; the cost of a region
+    anchor is the binary cross-entropy of its OWN class logits against the box's one-hot row plus ``iou_weight * -log(u)``, ``u`` the IoU
+    of its OWN decoded box with the box; the box gets ``k = clamp(int(sum of its candidate_topk largest u), 1, #region)`` positives, its
+    ``k`` region anchors smallest by (outside the box or the square, cost, anchor index); a candidate of several boxes goes to the
+    smallest (outside, cost), then the lowest box index.  Column 5 of a positive row is the box's score -- ``QualityFocalLoss(use_iou=True)``
+    forms YOLOX's IoU-aware class target from it.  There is no ignore band and NO force stage: a box without a region anchor has no
+    positive anchor.  One stated deviation from YOLOX: a box ranks only anchors of its own region.  The predictions are constants of the
+    step (detached here; nothing has a gradient).  The exact rule, operation by operation: ``ssdk_encode_ground_truth_simota`` in
+    include/ssdk.h."""
+
+    def __init__(self, center_radius=2.5, candidate_topk=10, iou_weight=3.0):
+        try:
+            ok = not isinstance(candidate_topk, (bool, str)) and int(candidate_topk) == candidate_topk and 1 <= candidate_topk <= SIMOTA_MAX_TOPK
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(f'SimOtaAssigner: candidate_topk={candidate_topk!r}, expected an integer in 1..{SIMOTA_MAX_TOPK}')
+        for name, v, strict in (('center_radius', center_radius, True), ('iou_weight', iou_weight, False)):
+            try:
+                ok = not isinstance(v, (str, bool)) and 0.0 <= float(v) < float('inf') and not (strict and float(v) == 0.0)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"SimOtaAssigner: {name}={v!r}, expected a finite number {'> 0' if strict else '>= 0'}")
+        self.center_radius, self.candidate_topk, self.iou_weight = float(center_radius), int(candidate_topk), float(iou_weight)
+        self._ws = None
+        self._levels = {}
+
+    def encode_ground_truth(self, ground_truth, anchors, prediction, box_coder, level_sizes=None, level_strides=None, return_box_idx=False,
+                            return_dynamic_k=False):
+        """Inputs and outputs as ``TaskAlignedAssigner.encode_ground_truth``; beside them ``level_sizes``, the anchor count of every pyramid
+        level in the anchors' order (``Detector.anchor_level_sizes(anchors)``), and ``level_strides``, per level ``(sx, sy)`` image pixels
+        per cell of its map or one number for both (``Detector.anchor_level_strides(anchors)``).  ``return_dynamic_k``: also the int32
+        ``[capacity]`` tensor of every box's ``k`` (after ``box_idx`` when both are asked for).  With an ``IntegralBoxCoder`` the loc head's
+        distributions are first integrated (``box_coder.integrate`` under ``no_grad``): one more pass over the loc logits than the loss
+        itself makes."""
+        if prediction is None or len(prediction) != 2:
+            raise ValueError('SimOtaAssigner.encode_ground_truth: prediction must be (scores, locs)')
+        if box_coder is None:
+            raise ValueError('SimOtaAssigner.encode_ground_truth: box_coder is required (its scales decode the predicted boxes)')
+        num_anchors = anchors.size(0)
+        if level_sizes is None or level_strides is None:
+            raise ValueError('SimOtaAssigner.encode_ground_truth: level_sizes and level_strides are required '
+                             '(Detector.anchor_level_sizes(anchors), Detector.anchor_level_strides(anchors))')
+        sizes = tuple(int(n) for n in level_sizes)
+        strides = tuple((float(s), float(s)) if not hasattr(s, '__len__') else (float(s[0]), float(s[1])) for s in level_strides)
+        if sum(sizes) != num_anchors:
+            raise ValueError(f'SimOtaAssigner.encode_ground_truth: level_sizes sum to {sum(sizes)}, the anchors are {num_anchors}')
+        if len(strides) != len(sizes) or not 1 <= len(sizes) <= SIMOTA_MAX_LEVELS:
+            raise ValueError(f'SimOtaAssigner.encode_ground_truth: {len(strides)} level_strides for {len(sizes)} levels (1..{SIMOTA_MAX_LEVELS})')
+        if not all(0.0 < v < float('inf') for s in strides for v in s):
+            raise ValueError(f'SimOtaAssigner.encode_ground_truth: level_strides={strides!r} must be finite and positive')
+        scores, locs = prediction
+        _lib.require_cuda(anchors, scores, locs)
+        key = (sizes, strides)
+        if key not in self._levels:
+            self._levels[key] = ((ctypes.c_int32 * len(sizes))(*sizes), (ctypes.c_float * (2 * len(sizes)))(*[v for s in strides for v in s]))
+        c_sizes, c_strides = self._levels[key]
+        lib = _lib.lib()
+        device = anchors.device
+        batch_size = len(ground_truth)
+        anchors = anchors.contiguous().float()
+        with torch.no_grad():
+            scores, locs = scores.detach(), locs.detach()
+            if hasattr(box_coder, 'integrate'):
+                locs = box_coder.integrate(locs, num_anchors)
+            scores, locs = scores.float().contiguous(), locs.float().contiguous()
+        if scores.shape[0] != batch_size or locs.shape[0] != batch_size or locs.numel() != batch_size * num_anchors * 4:
+            raise ValueError(f'SimOtaAssigner.encode_ground_truth: locs of shape {tuple(locs.shape)} / scores of shape '
+                             f'{tuple(scores.shape)} for a batch of {batch_size} and {num_anchors} anchors')
+        num_columns, rest = divmod(scores.numel(), batch_size * num_anchors)
+        if rest or num_columns < 1:
+            raise ValueError(f'SimOtaAssigner.encode_ground_truth: scores of shape {tuple(scores.shape)} are not [Batch, {num_anchors} * C]')
+        if isinstance(ground_truth, PackedGroundTruth):
+            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
+        else:
+            rows, offs, total = pack_ground_truth(ground_truth, device)
+        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
+        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
+        dynamic_k = torch.empty((max(total, 1),), dtype=torch.int32, device=device)[:total] if return_dynamic_k else None
+        need = lib.ssdk_encode_ground_truth_simota_workspace_bytes(batch_size, total, num_anchors, len(sizes))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
+        _lib.check(lib.ssdk_encode_ground_truth_simota(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors,
+                                                       c_sizes, c_strides, len(sizes), _lib.ptr(scores), num_columns, _lib.ptr(locs),
+                                                       float(box_coder.xy_scale), float(box_coder.wh_scale), self.center_radius,
+                                                       self.candidate_topk, self.iou_weight, _lib.ptr(target), _lib.ptr(box_idx),
+                                                       _lib.ptr(dynamic_k) if total else None, _lib.ptr(self._ws), self._ws.numel(),
+                                                       _lib.current_stream()),
+                   'ssdk_encode_ground_truth_simota')
+        # keep the staging tensors alive until the stream has consumed them
+        target._ssdk_keepalive = (rows, offs, scores, locs)
+        out = (target,) + ((box_idx,) if return_box_idx else ()) + ((dynamic_k,) if return_dynamic_k else ())
+        return out if len(out) > 1 else target

@@ -1,0 +1,166 @@
+"""GPU: SimOtaAssigner / matcher.match_simota (ssdk_encode_ground_truth_simota) against the numpy restatement of the rule that
+tests/test_simota.py pins to hand-worked cases.  Every generated case keeps a margin at each of its decisions (checked on the CPU in
+tests/simota_cases.py), so ``box_idx``, ``dynamic_k`` and all six target columns are compared exactly: no tolerance anywhere."""
+import numpy as np
+import pytest
+import torch
+
+import simota_cases as sc
+from single_shot_detection_amd.detection import matcher
+from single_shot_detection_amd.detection.box_coder import BoxCoder, IntegralBoxCoder
+from single_shot_detection_amd.detection.target_assigner import PackedGroundTruth, SimOtaAssigner
+
+pytestmark = pytest.mark.gpu
+
+
+def bits(a):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def tensors(gt_list):
+    return [torch.from_numpy(np.ascontiguousarray(g, np.float32).reshape(-1, 6)) for g in gt_list]
+
+
+def coder():
+    return BoxCoder(sc.XY_SCALE, sc.WH_SCALE)
+
+
+def embedded(t, pad=64):
+    """A copy of ``t`` in the middle of an allocation whose every other byte is 0xFF (a NaN to whatever reads past an end)."""
+    nbytes = t.numel() * t.element_size()
+    buf = torch.full((nbytes + 2 * pad,), 0xFF, dtype=torch.uint8, device='cuda')
+    view = buf[pad:pad + nbytes].view(t.dtype).view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def encode(gt, anchors, scores, locs, sizes, strides, kw, assigner=None, box_coder=None):
+    sa = assigner or SimOtaAssigner(**kw)
+    t, idx, k = sa.encode_ground_truth(gt if isinstance(gt, PackedGroundTruth) else tensors(gt), anchors, (scores, locs), box_coder or coder(),
+                                       level_sizes=sizes, level_strides=strides, return_box_idx=True, return_dynamic_k=True)
+    assert t.is_cuda and t.dtype == torch.float32 and idx.dtype == torch.int32 and k.dtype == torch.int32
+    return t, idx, k
+
+
+def check(name, t, idx, k, gt, ref_idx, ref_k):
+    """box_idx, dynamic_k and the six target columns, exactly."""
+    got_idx, got_k = idx.cpu().numpy(), k.cpu().numpy()
+    ref_k = np.concatenate(ref_k) if len(ref_k) else np.zeros(0, np.int32)
+    print(f'{name}: positives {int((ref_idx >= 0).sum())}, boxes {len(ref_k)}, k_g from {ref_k.min() if len(ref_k) else 0} to '
+          f'{ref_k.max() if len(ref_k) else 0}; anchors that differ {int((got_idx != ref_idx).sum())}, '
+          f'counts that differ {int((got_k[:len(ref_k)] != ref_k).sum())}')
+    assert np.array_equal(got_k[:len(ref_k)], ref_k), (name, got_k[:len(ref_k)].tolist(), ref_k.tolist())
+    assert (got_k[len(ref_k):] == 0).all()
+    assert np.array_equal(got_idx, ref_idx), (name, int((got_idx != ref_idx).sum()))
+    assert np.array_equal(bits(t), bits(sc.target_np(ref_idx, gt))), name
+
+
+@pytest.mark.parametrize('q', sorted({c[2] for c in sc.GRID_CASES.values()}))
+def test_hand_worked_grid(q):
+    """The hand-worked images of one candidate_topk as one batch (every logit 0, every predicted box its anchor or off the image)."""
+    names = [n for n in sc.GRID_CASES if sc.GRID_CASES[n][2] == q]
+    gt = [sc.grid_gt(n) for n in names]
+    pred = [sc.grid_prediction(n) for n in names]
+    scores, locs = np.stack([p[0] for p in pred]), np.stack([p[1] for p in pred])
+    expected = [sc.grid_expected(n) for n in names]
+    ref_idx, ref_k = np.stack([e[0] for e in expected]), [e[1] for e in expected]
+    anchors_np = sc.grid_anchors()
+    kw = dict(center_radius=sc.GRID_RADIUS, candidate_topk=q)
+    for dtype in (np.float32, np.float64):
+        idx_np, k_np = sc.simota_np(gt, anchors_np, scores, locs, sc.GRID_LEVELS, sc.GRID_STRIDES, dtype=dtype, **kw)
+        assert np.array_equal(idx_np, ref_idx) and all(np.array_equal(a, b) for a, b in zip(k_np, ref_k))
+    t, idx, k = encode(gt, torch.from_numpy(anchors_np).cuda(), torch.from_numpy(scores).reshape(len(names), -1).cuda(),
+                       torch.from_numpy(locs).reshape(len(names), -1).cuda(), sc.GRID_LEVELS, sc.GRID_STRIDES, kw)
+    assert np.array_equal(idx.cpu().numpy(), ref_idx), {n: np.nonzero(r >= 0)[0].tolist() for n, r in zip(names, idx.cpu().numpy())}
+    check(f'grid q={q}', t, idx, k, gt, ref_idx, ref_k)
+
+
+@pytest.mark.parametrize('name', list(sc.GENERATED))
+def test_generated_cases_equal_the_restatement(name):
+    gt, anchors_np, scores_np, locs_np, sizes, strides, kw, fig = sc.generated(name)
+    anchors, scores, locs = (torch.from_numpy(x).cuda() for x in (anchors_np, scores_np, locs_np))
+    sa = SimOtaAssigner(**kw)
+    t, idx, k = encode(gt, anchors, scores, locs, sizes, strides, kw, sa)
+    check(name, t, idx, k, gt, fig['idx64'], fig['k64'])
+    t2, idx2, k2 = encode(gt, anchors, scores, locs, sizes, strides, kw, sa)                       # two runs: identical bits
+    assert torch.equal(idx, idx2) and torch.equal(k, k2) and np.array_equal(bits(t), bits(t2))
+    # a PackedGroundTruth whose capacity exceeds its rows (garbage in the padding): the same bits as the list form, k_g = 0 in the padding
+    total = sum(len(g) for g in gt)
+    packed = PackedGroundTruth.from_list(tensors(gt), anchors.device, capacity=total + 37)
+    packed.rows[total:] = torch.from_numpy(np.random.default_rng(5).uniform(1.0, 200.0, (37, 6)).astype(np.float32)).cuda()
+    t3, idx3, k3 = encode(packed, anchors, scores, locs, sizes, strides, kw, sa)
+    assert torch.equal(idx, idx3) and np.array_equal(bits(t), bits(t3))
+    assert k3.shape == (total + 37,) and torch.equal(k3[:total], k) and (k3[total:] == 0).all()
+    # without box_idx and dynamic_k (both NULL): the same target
+    t4 = sa.encode_ground_truth(tensors(gt), anchors, (scores, locs), coder(), level_sizes=sizes, level_strides=strides)
+    assert isinstance(t4, torch.Tensor) and np.array_equal(bits(t), bits(t4))
+    # every input in the middle of an allocation of 0xFF bytes: nothing is read past an end
+    rows = torch.from_numpy(np.concatenate([np.asarray(g, np.float32).reshape(-1, 6) for g in gt])).cuda()
+    offs = torch.from_numpy(np.concatenate([[0], np.cumsum([len(g) for g in gt])]).astype(np.int32)).cuda()
+    t5, idx5, k5 = encode(PackedGroundTruth(embedded(rows), embedded(offs)), embedded(anchors), embedded(scores), embedded(locs), sizes, strides,
+                          kw, sa)
+    assert torch.equal(idx, idx5) and torch.equal(k, k5) and np.array_equal(bits(t), bits(t5))
+
+
+def test_match_simota_is_row_0_of_the_batch_form():
+    gt, anchors_np, scores_np, locs_np, sizes, strides, kw, fig = sc.generated('mb2_g32')
+    anchors = torch.from_numpy(anchors_np).cuda()
+    A = len(anchors_np)
+    scores, locs = torch.from_numpy(scores_np[0]).cuda().view(A, -1), torch.from_numpy(locs_np[0]).cuda().view(A, 4)
+    g = torch.from_numpy(gt[0]).cuda()
+    one = matcher.match_simota(g[:, :4], g[:, 4], anchors, scores, locs, coder(), sizes, strides, **kw)
+    assert one.dtype == torch.int64 and one.shape == (A,)
+    assert np.array_equal(one.cpu().numpy(), fig['idx64'][0])
+    none = matcher.match_simota(torch.zeros((0, 4), device='cuda'), torch.zeros((0,), device='cuda'), anchors, scores, locs, coder(), sizes,
+                                strides)
+    assert (none == matcher.NOT_MATCHED).all()
+
+
+def test_integral_box_coder_equals_the_assigner_on_the_integrated_locs():
+    gt, anchors_np, scores_np, _, sizes, strides, kw, _ = sc.generated('mb2_one_empty')
+    anchors, scores = torch.from_numpy(anchors_np).cuda(), torch.from_numpy(scores_np).cuda()
+    ibc = IntegralBoxCoder(sc.XY_SCALE, sc.WH_SCALE, reg_max=7, xy_limit=4.0, wh_limit=3.0)
+    A = len(anchors_np)
+    logits = torch.from_numpy(np.random.default_rng(23).standard_normal((len(gt), A * 4 * ibc.bins), dtype=np.float32) * 2).cuda().requires_grad_(True)
+    t, idx, k = encode(gt, anchors, scores, logits, sizes, strides, kw, box_coder=ibc)
+    assert not t.requires_grad and logits.grad is None
+    with torch.no_grad():
+        locs = ibc.integrate(logits, A)
+    t2, idx2, k2 = encode(gt, anchors, scores, locs, sizes, strides, kw)
+    assert (idx >= 0).any() and torch.equal(idx, idx2) and torch.equal(k, k2) and np.array_equal(bits(t), bits(t2))
+
+
+def test_python_layer_refuses_bad_predictions():
+    anchors = torch.from_numpy(sc.grid_anchors()).cuda()
+    gt = tensors([sc.grid_gt('sum_just_above_1')])
+    scores, locs = torch.zeros((1, 42 * 3), device='cuda'), torch.zeros((1, 42 * 4), device='cuda')
+    sa = SimOtaAssigner(0.5)
+    lv = dict(level_sizes=sc.GRID_LEVELS, level_strides=sc.GRID_STRIDES)
+    with pytest.raises(ValueError):
+        sa.encode_ground_truth(gt, anchors, (scores, locs[:, :-4]), coder(), **lv)
+    with pytest.raises(ValueError):
+        sa.encode_ground_truth(gt, anchors, (scores[:, :-1], locs), coder(), **lv)
+    with pytest.raises(ValueError):
+        sa.encode_ground_truth(gt, anchors, (scores, locs), coder(), level_sizes=(32, 9), level_strides=(16.0, 32.0))
+    t, k = sa.encode_ground_truth(gt, anchors, (scores, locs), coder(), return_dynamic_k=True, **lv)     # (the good call, and k alone)
+    assert k.tolist() == [2] and int((t[0, :, 4] > 0).sum()) == 2
+
+
+def test_captured_graph_and_detection_init_in_a_child_process():
+    """tests/simota_graph_worker.py, in a process of its own (see there): the call captured in a HIP graph and replayed on two batches
+    equals the eager results; one training step (eager and with graph_hot_path=True) through detection.init with
+    target_assigner = {'name': 'SimOtaAssigner'}, valid_sampler, QualityFocalLoss and IoULoss: the loss is the existing loss path's on the
+    restatement's target."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(repo, 'tests', 'simota_graph_worker.py')], cwd=repo, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.returncode, out.stdout[-2000:], out.stderr[-3000:])
+    res = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+    print(res)
+    assert res['timeouts'] == 0
+    assert all(np.isfinite(res[k]) for k in ('eager_loss', 'graphed_loss')), res
