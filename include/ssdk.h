@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SSDK_VERSION 132
+#define SSDK_VERSION 133
 
 #define SSDK_OK 0
 #define SSDK_E_INVALID (-1)   /* bad argument / shape */
@@ -910,6 +910,87 @@ int ssdk_mixup_images(const float* in, float* out, int batch, long long per_imag
                       double lam, void* stream);
 int ssdk_mixup_ground_truth(const float* rows_in, int gt_stride, const int* offsets_in, int batch, const int* index,
                             const unsigned char* roll, double lam, float* rows_out, int* offsets_out, void* stream);
+
+/* ---- device-side SSD augmentation (ABI 133) ------------------------------------------------------------
+ * bf/preprocessing/transforms.py in its one supported order: RandomAdjustHueSaturation, ToFloat, RandomAdjustBrightness,
+ * RandomAdjustContrast, RandomExpand, RandomCrop, RandomHorizontalFlip / RandomVerticalFlip, Resize, ToFloatTensor, Normalize, every
+ * step optional but the resize.  The random draws are the caller's: one ssdk_augment_params per image plus a table of candidate crop
+ * windows.  The source images lie in ONE ragged uint8 buffer, interleaved RGB rows (HWC), each found by its ssdk_augment_image.
+ *
+ * Geometry.  The expand puts the image at (expand_x, expand_y) of a canvas expand_w x expand_h filled with the image's scalar mean;
+ * the crop takes a window of that canvas; the flips mirror the window; the resize maps it onto out_w x out_h, bilinear with half-pixel
+ * centres, src = (dst + 0.5) * (win / out) - 0.5, taps clamped to the WINDOW, no antialiasing.  The composition is one window in source
+ * coordinates (windows[b] = x, y, w, h; x and y may be negative, the window may reach past the source on every side): a tap inside the
+ * source reads its three bytes and applies the colour steps, a tap outside is the fill.
+ *
+ * Colour, on a source pixel (r, g, b), fp32:
+ *   SSDK_AUG_HUE_SATURATION  float HSV: v = max, c = max - min, s = c / v (0 at v = 0), h in sextants; h += hue_delta * 6 (that is
+ *                            hue_delta * 360 degrees, modulo 360), s = clip(s * saturation, 0, 1); back to RGB
+ *                            channel(n) = v - v s max(0, min(k, 4 - k, 1)), k = (n + h) mod 6, n = 5, 3, 1 for r, g, b.
+ *                            (The reference goes through cv2's 8-bit HSV; this is not bit-compatible with it, by design.)
+ *   SSDK_AUG_BRIGHTNESS      x = clip(x + brightness, 0, 255)            (brightness = u * 255, already multiplied)
+ *   SSDK_AUG_CONTRAST        x = clip(mean_c + contrast * (x - mean_c), 0, 255), mean_c the per-channel mean of the image after the steps above
+ *   fill                     the mean over all channels of the image after the contrast step
+ * Both means are fp64 sums over a fixed partition in a fixed order (no floating-point atomics: the same bits run to run), the quotient
+ * taken in fp64 and rounded to float once. */
+#define SSDK_AUG_HUE_SATURATION 1
+#define SSDK_AUG_BRIGHTNESS 2
+#define SSDK_AUG_CONTRAST 4
+#define SSDK_AUG_EXPAND 8
+#define SSDK_AUG_CROP 16      /* try the candidates; without it the window is the whole canvas and attempt_out is -2 */
+#define SSDK_AUG_HFLIP 32
+#define SSDK_AUG_VFLIP 64
+#define SSDK_AUG_KEEP_IOU 128 /* keep_criterion 'iou'; without it 'center_point' */
+
+typedef struct ssdk_augment_image {
+    long long offset; /* of the image's first byte in the source buffer */
+    int height, width;
+} ssdk_augment_image;
+
+typedef struct ssdk_augment_params {
+    int flags; /* SSDK_AUG_* */
+    float hue_delta, saturation, brightness, contrast;
+    int expand_w, expand_h, expand_x, expand_y; /* canvas size and the image's origin in it (SSDK_AUG_EXPAND) */
+    float min_iou;
+    int min_objects_kept;
+    int reserved;
+} ssdk_augment_params;
+
+/*
+ * Stage 1: window choice and boxes (functional/box.py, functional/img.py:55-83, detection_dataset.py:31-32), float32 op for op.
+ *   images, params   DEV [batch]
+ *   candidates       DEV int32 [batch, attempts, 4]: (xmin, ymin, w, h) in the canvas; w <= 0 marks a candidate the host found larger than
+ *                    the image (img.py:69-70).  A candidate that does not lie inside the canvas is skipped as well.
+ *   rows_in          DEV fp32 [total_rows, gt_stride] + offsets_in DEV int32 [batch + 1], as for ssdk_encode_ground_truth; gt_stride >= 4
+ *   rows_out         DEV fp32 [total_rows, gt_stride]: the surviving rows back to back, image after image, in input order; columns 4 and up
+ *                    unchanged; rows past offsets_out[batch] are not written.  offsets_out DEV int32 [batch + 1].
+ *   attempt_out      DEV int32 [batch]: index of the accepted candidate, -1 if none was (the image stays uncropped), -2 without SSDK_AUG_CROP
+ *   windows_out      DEV int32 [batch, 4]: the window in source coordinates, for ssdk_augment_images
+ * With region = [xmin, ymin, xmin + w - 1, ymin + h - 1]: a box's new corners are its zero_incorrect intersection with the region; iou is
+ * that of the box with its own clipped version; the candidate is accepted when max(iou) > min_iou (strictly; a NaN iou rejects every
+ * candidate) and at least min_objects_kept boxes stay -- those whose centre lies strictly inside the region, or whose own iou > min_iou with
+ * SSDK_AUG_KEEP_IOU.  An image without boxes accepts its first valid candidate.  Accepted boxes are shifted by the window's origin and
+ * clipped to [0, w - 1] x [0, h - 1]; a flip is (width - 1 - x) with the corners swapped; the resize multiplies by float(out_w / width)
+ * and clips to [0, out_w - 1]; boxes with x1 == x2 or y1 == y2 are then dropped.
+ * Two launches, no allocation, no synchronisation.
+ */
+size_t ssdk_augment_boxes_workspace_bytes(int batch);
+int ssdk_augment_boxes(const ssdk_augment_image* images, const ssdk_augment_params* params, const int* candidates, int attempts,
+                       const float* rows_in, int gt_stride, const int* offsets_in, int batch, int total_rows, int out_w, int out_h,
+                       float* rows_out, int* offsets_out, int* attempt_out, int* windows_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/*
+ * Stages 2 and 3: the two statistics passes and the gather, given the windows.
+ *   src [src_bytes]  DEV uint8: the ragged image buffer.  An image whose descriptor does not fit into it is read nowhere and is all fill.
+ *   windows          DEV int32 [batch, 4] (ssdk_augment_boxes' windows_out, or the caller's own)
+ *   divide_255       ToFloatTensor(normalize=True);  mean_std HOST float [6]: Normalize's mean[3] then std[3] (std != 0), read during the call
+ *   out              DEV fp32 [batch, 3, out_h, out_w] = ((v / 255) - mean) / std
+ * Three launches (both statistics passes leave at once for images that do not need them), no allocation, no synchronisation.
+ */
+size_t ssdk_augment_images_workspace_bytes(int batch);
+int ssdk_augment_images(const unsigned char* src, long long src_bytes, const ssdk_augment_image* images, const ssdk_augment_params* params,
+                        const int* windows, int batch, int out_w, int out_h, int divide_255, const float* mean_std, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- evaluation metric -----------------------------------------------------------------------------
  * detection/metrics/mean_average_precision.py:10-116  mean_average_precision(predictions, gts, class_labels, iou_threshold, voc)
