@@ -26,6 +26,10 @@
 // And ssdk_encode_ground_truth_simota (not in the reference either): SimOTA, three launches of its own -- simota_class_sum_kernel (per region
 // anchor the softplus sum of its logits, the class cost's per-anchor part), simota_candidates_kernel (one workgroup per box: the count k_g
 // from its largest IoUs, then its k_g cheapest region anchors as a cutoff key) and simota_assign_kernel; see further down.
+// The three later assigners share their building blocks, which stand in front of the kernels: the 64-bit keys, the
+// four-in-flight anchor sweep, the two-keys-in-registers keeper, the workgroup's pop step with its advance, the chunk loop of the
+// (image, anchor) kernels, the level table.  On the host one checker, one level-table builder and one carve function per assigner serve the
+// ssdk_encode_ground_truth* entry points.
 // IoU is computed op for op like the reference (this TU is built -ffp-contract=off, IEEE divide) so that
 // assignments are bit-exact.
 #include "common.h"
@@ -35,6 +39,118 @@ namespace ssdk {
 constexpr int kAssignThreads = 256;
 constexpr int kGtChunk = 128;
 constexpr int kSegAnchors = 512;  // anchors swept by one wave of gt_argmax_kernel
+
+// ---- what the assigners share -------------------------------------------------------------------------------------
+// 64-bit keys: the value's order-preserving bits on top, below them ~index, so that the LARGER key is the larger value, then the lower index.
+constexpr unsigned kOrdZero = 0x80000000u;  // ord_f32(0.0f)
+__device__ __forceinline__ unsigned key_hi(unsigned long long k) { return (unsigned)(k >> 32); }
+__device__ __forceinline__ int key_col(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); }
+__device__ __forceinline__ unsigned long long make_key(unsigned hi, int idx) { return ((unsigned long long)hi << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)idx); }
+// Order-preserving bits of any float: -inf < ... < -0 == +0 < ... < +inf, all above 0; NaN -> 0, below everything (it never wins).
+__device__ __forceinline__ unsigned ord_f32(float v) {
+    if (v != v) return 0u;
+    if (v == 0.0f) return kOrdZero;
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+struct OpMinU64 {
+    __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a < b ? a : b; }
+};
+// The two orders a workgroup pops keys in: which key comes first, and the key that comes after every real one.
+template <typename Op> struct KeyOrder;
+template <> struct KeyOrder<OpMinU64> {
+    static constexpr unsigned long long none = ~0ull;
+    static __device__ __forceinline__ bool before(unsigned long long a, unsigned long long b) { return a < b; }
+};
+template <> struct KeyOrder<OpMaxU64> {
+    static constexpr unsigned long long none = 0ull;
+    static __device__ __forceinline__ bool before(unsigned long long a, unsigned long long b) { return a > b; }
+};
+
+__device__ __forceinline__ float2 box_centre(float4 gb) { return make_float2((gb.x + gb.z) * 0.5f, (gb.y + gb.w) * 0.5f); }
+__device__ __forceinline__ bool centre_inside(float4 gb, float4 p) { return gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w; }   // strictly
+// column of the box's class in a row of logits, or -1 (the class is none of the columns: s = 0)
+__device__ __forceinline__ int class_column(float cls, int C) { return (cls >= 1.0f && cls <= (float)C) ? (int)cls - 1 : -1; }
+// image of row g (< gt_off[batch]): the last i with gt_off[i] <= g
+__device__ __forceinline__ int image_of_row(const int32_t* __restrict__ gt_off, int batch, int g) {
+    int lo = 0, hi = batch - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (gt_off[mid] <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// Pyramid levels by value (no table to upload): level l owns anchors [off[l], off[l + 1]); the entries past n repeat the total.
+struct Levels { int n; int off[SSDK_ATSS_MAX_LEVELS + 1]; };
+
+// The workgroup's kThreads threads sweep anchors [a_begin, a_end) with four 16-byte loads in flight; `take(a, p)` sees a thread's anchors
+// in ascending order.
+template <int kThreads, typename Take>
+__device__ __forceinline__ void sweep_anchors(const float4* __restrict__ anchors, int a_begin, int a_end, const Take& take) {
+    int a = a_begin + threadIdx.x;
+    for (; a + 3 * kThreads < a_end; a += 4 * kThreads) {
+        const float4 p0 = anchors[a], p1 = anchors[a + kThreads], p2 = anchors[a + 2 * kThreads], p3 = anchors[a + 3 * kThreads];
+        take(a, p0);
+        take(a + kThreads, p1);
+        take(a + 2 * kThreads, p2);
+        take(a + 3 * kThreads, p3);
+    }
+    for (; a < a_end; a += kThreads) take(a, anchors[a]);
+}
+// A thread's two first keys of a sweep stay in registers (selects: the branchy form made the compiler keep k1 and k2 in scratch).  Its
+// anchors are kThreads apart, the anchors of one cell and of neighbouring cells are not, so a thread almost never owns more than one of a
+// box's candidates.
+template <typename Op>
+__device__ __forceinline__ void keep_two(unsigned long long k, unsigned long long& k1, unsigned long long& k2) {
+    const bool b1 = KeyOrder<Op>::before(k, k1), b2 = KeyOrder<Op>::before(k, k2);
+    k2 = b1 ? k1 : (b2 ? k : k2);
+    k1 = b1 ? k : k1;
+}
+// First key of the workgroup, returned to every thread: `red` = LDS [kThreads / kWave], one barrier; `red` is read after it, so the next
+// call needs another array (or a barrier in between).
+template <typename Op, int kThreads>
+__device__ __forceinline__ unsigned long long block_first(unsigned long long k, unsigned long long* red) {
+    k = wave_allreduce(k, Op());
+    if (lane_id() == 0) red[threadIdx.x >> 6] = k;
+    __syncthreads();
+    unsigned long long r = red[0];
+#pragma unroll
+    for (int q = 1; q < kThreads / kWave; ++q) r = Op()(red[q], r);
+    return r;
+}
+// One pop of the workgroup's first remaining key (`cur`: the thread's), one barrier: the two halves of s_red alternate with `step`, which
+// counts EVERY pop of the kernel.
+template <typename Op, int kThreads>
+__device__ __forceinline__ unsigned long long pop_first(unsigned long long cur, unsigned long long (*s_red)[kThreads / kWave], int step) {
+    return block_first<Op, kThreads>(cur, s_red[step & 1]);
+}
+// After a pop: the owner of the popped key moves on to its second key (k1, k2: keep_two's); only a thread that loses both calls `rescan`,
+// which re-reads its own anchors for the next key behind the popped one (next_key_behind).
+template <typename Rescan>
+__device__ __forceinline__ void pop_advance(unsigned long long popped, unsigned long long& cur, unsigned long long k1, unsigned long long k2, Rescan rescan) {
+    if (cur == popped) cur = cur == k1 ? k2 : rescan();   // (k2 is `none` when the thread swept a single key: it has nothing left)
+}
+template <typename Op, int kThreads, typename KeyOf>
+__device__ __forceinline__ unsigned long long next_key_behind(unsigned long long popped, int a_begin, int a_end, KeyOf key_of) {
+    unsigned long long cur = KeyOrder<Op>::none;
+    for (int b = a_begin + threadIdx.x; b < a_end; b += kThreads) {
+        const unsigned long long k = key_of(b);   // (`none` for an anchor without a key)
+        if (KeyOrder<Op>::before(popped, k) && KeyOrder<Op>::before(k, cur)) cur = k;
+    }
+    return cur;
+}
+// One thread per (image, anchor): the image's G boxes pass through the kernel's own LDS arrays in chunks of kGtChunk.  `load(k, j)` puts box
+// k of the image into slot j (one thread per box); `visit(base, n)` then sees boxes base .. base + n - 1 in slots 0 .. n - 1.
+template <typename Load, typename Visit>
+__device__ __forceinline__ void for_box_chunks(int G, const Load& load, const Visit& visit) {
+    for (int base = 0; base < G; base += kGtChunk) {
+        const int n = min(kGtChunk, G - base);
+        __syncthreads();
+        if (threadIdx.x < n) load(base + (int)threadIdx.x, (int)threadIdx.x);
+        __syncthreads();
+        visit(base, n);
+    }
+}
 
 // One workgroup per ground-truth box: its 1 024 threads sweep ALL anchors and the result is stored, not accumulated -- no atomics and
 // therefore no zero-fill launch in front (the first version folded (box, 512-anchor segment) partial results into a zeroed array with
@@ -66,8 +182,10 @@ __global__ void __launch_bounds__(kArgmaxThreads) gt_argmax_kernel(const float* 
         const float v = iou_corner(gb, garea, c, area4(c.x, c.y, c.z, c.w));
         if (bi < 0 || v > best || (v != v && best == best)) { best = v; bi = a; }
     };
+    // sweep_anchors spelled out (this kernel is on the training step's path, and through the helper its code came out different): taken in
+    // ascending anchor order, first-index ties
     int a = a_begin + threadIdx.x;
-    for (; a + 3 * kArgmaxThreads < A; a += 4 * kArgmaxThreads) {   // four loads in flight, taken in ascending anchor order (first-index ties)
+    for (; a + 3 * kArgmaxThreads < A; a += 4 * kArgmaxThreads) {
         const float4 p0 = anchors[a], p1 = anchors[a + kArgmaxThreads], p2 = anchors[a + 2 * kArgmaxThreads], p3 = anchors[a + 3 * kArgmaxThreads];
         take(a, p0);
         take(a + kArgmaxThreads, p1);
@@ -76,7 +194,7 @@ __global__ void __launch_bounds__(kArgmaxThreads) gt_argmax_kernel(const float* 
     }
     for (; a < A; a += kArgmaxThreads) take(a, anchors[a]);
     unsigned long long key = 0ull;
-    if (bi >= 0) key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)bi);
+    if (bi >= 0) key = make_key(__float_as_uint(best), bi);
     key = wave_allreduce(key, OpMaxU64());
     if (lane == 0) s_key[wave] = key;
     __syncthreads();
@@ -134,7 +252,7 @@ __global__ void __launch_bounds__(kAssignThreads) assign_kernel(const float* __r
     }
     float best = 0.0f;
     int bi = SSDK_NOT_MATCHED, forced = -1;
-    for (int base = 0; base < G; base += kGtChunk) {
+    for (int base = 0; base < G; base += kGtChunk) {   // for_box_chunks spelled out (on the training step's path, as gt_argmax_kernel)
         const int n = min(kGtChunk, G - base);
         __syncthreads();
         if (threadIdx.x < n) {
@@ -145,7 +263,7 @@ __global__ void __launch_bounds__(kAssignThreads) assign_kernel(const float* __r
             s_area[threadIdx.x] = area4(gb.x, gb.y, gb.z, gb.w);
             unsigned long long key = gt_best[(size_t)g * segs];
             for (int q = 1; q < segs; ++q) { const unsigned long long k2 = gt_best[(size_t)g * segs + q]; key = k2 > key ? k2 : key; }
-            s_best_anchor[threadIdx.x] = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+            s_best_anchor[threadIdx.x] = key_col(key);
         }
         __syncthreads();
         for (int k = 0; k < n; ++k) {
@@ -225,26 +343,10 @@ constexpr int kBipThreads = 1024;
 constexpr int kBipWaves = kBipThreads / kWave;
 constexpr int kBipLdsBoxes = 1024;        // per image: more boxes than this keep their keys in the workspace instead of LDS (same code, flat pointers)
 constexpr int kBipMaxAnchors = 262144;    // the taken-column bit mask of the fused form is 32 KB of LDS
-constexpr unsigned kOrdZero = 0x80000000u;  // ord_f32(0.0f)
 
-__device__ __forceinline__ unsigned key_hi(unsigned long long k) { return (unsigned)(k >> 32); }
-__device__ __forceinline__ int key_col(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); }
-__device__ __forceinline__ unsigned long long make_key(unsigned hi, int idx) { return ((unsigned long long)hi << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)idx); }
-// Order-preserving bits of any float: -inf < ... < -0 == +0 < ... < +inf, all above 0; NaN -> 0, below everything (it never wins).
-__device__ __forceinline__ unsigned ord_f32(float v) {
-    if (v != v) return 0u;
-    if (v == 0.0f) return kOrdZero;
-    const unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // Maximum of a key over the workgroup, returned to every thread.  `red` = LDS [kBipWaves]; two barriers, `red` is free again afterwards.
 __device__ __forceinline__ unsigned long long bip_block_max(unsigned long long k, unsigned long long* red) {
-    k = wave_allreduce(k, OpMaxU64());
-    if (lane_id() == 0) red[threadIdx.x >> 6] = k;
-    __syncthreads();
-    unsigned long long r = red[0];
-#pragma unroll
-    for (int i = 1; i < kBipWaves; ++i) { const unsigned long long t = red[i]; r = t > r ? t : r; }
+    const unsigned long long r = block_first<OpMaxU64, kBipThreads>(k, red);
     __syncthreads();
     return r;
 }
@@ -415,15 +517,9 @@ __global__ void __launch_bounds__(256) copy_f32_kernel(const float* __restrict__
 constexpr int kAtssThreads = 1024;
 constexpr int kAtssWaves = kAtssThreads / kWave;
 constexpr unsigned long long kAtssNoKey = ~0ull;   // above every key (an anchor index is below 2^31)
-struct AtssLevels { int n; int off[SSDK_ATSS_MAX_LEVELS + 1]; };   // level l owns anchors [off[l], off[l + 1]); by value: no table to upload
 
-struct OpMinU64 {
-    __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a < b ? a : b; }
-};
-
-// (gcx, gcy) of a box, then an anchor's key against it: two subtractions, two products, one add, all fp32 and uncontracted.  The sum of two
-// squares is never negative, so its bits order like the value; NaN goes above +inf.
-__device__ __forceinline__ float2 atss_centre(float4 gb) { return make_float2((gb.x + gb.z) * 0.5f, (gb.y + gb.w) * 0.5f); }
+// An anchor's key against a box centre gc = box_centre(gb): two subtractions, two products, one add, all fp32 and uncontracted.  The sum of
+// two squares is never negative, so its bits order like the value; NaN goes above +inf.
 __device__ __forceinline__ unsigned long long atss_key(float4 p, float2 gc, int a) {
     const float dx = p.x - gc.x, dy = p.y - gc.y;
     const float d2 = dx * dx + dy * dy;
@@ -432,7 +528,7 @@ __device__ __forceinline__ unsigned long long atss_key(float4 p, float2 gc, int 
 }
 
 __global__ void __launch_bounds__(kAtssThreads) atss_candidates_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
-                                                                       int batch, const float4* __restrict__ anchors, AtssLevels lv, int topk,
+                                                                       int batch, const float4* __restrict__ anchors, Levels lv, int topk,
                                                                        unsigned long long* __restrict__ cutoff, float* __restrict__ cand_iou) {
     __shared__ unsigned long long s_red[2][kAtssWaves];
     const int g = blockIdx.x, l = blockIdx.y;
@@ -442,49 +538,19 @@ __global__ void __launch_bounds__(kAtssThreads) atss_candidates_kernel(const flo
     for (int q = 0; q < SSDK_ATSS_MAX_LEVELS; ++q)   // (constant indices: a by-value table indexed by a variable would be copied to scratch)
         if (q == l) { a_begin = lv.off[q]; a_end = lv.off[q + 1]; }
     const int kk = min(topk, a_end - a_begin);
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
     const float* r = gt_rows + (size_t)g * gt_stride;
     const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
-    const float2 gc = atss_centre(gb);
-    // The sweep: the thread's two smallest keys stay in registers.  Its anchors are kAtssThreads apart, the anchors of one cell and of
-    // neighbouring cells are not, so a thread almost never owns more than one of a box's candidates.
-    unsigned long long k1 = kAtssNoKey, k2 = kAtssNoKey;
-    auto take = [&](int a, const float4& p) {
-        const unsigned long long k = atss_key(p, gc, a);
-        const bool lt1 = k < k1, lt2 = k < k2;   // (selects: the branchy form made the compiler keep k1 and k2 in scratch)
-        k2 = lt1 ? k1 : (lt2 ? k : k2);
-        k1 = lt1 ? k : k1;
-    };
-    int a = a_begin + threadIdx.x;
-    for (; a + 3 * kAtssThreads < a_end; a += 4 * kAtssThreads) {   // four loads in flight
-        const float4 p0 = anchors[a], p1 = anchors[a + kAtssThreads], p2 = anchors[a + 2 * kAtssThreads], p3 = anchors[a + 3 * kAtssThreads];
-        take(a, p0);
-        take(a + kAtssThreads, p1);
-        take(a + 2 * kAtssThreads, p2);
-        take(a + 3 * kAtssThreads, p3);
-    }
-    for (; a < a_end; a += kAtssThreads) take(a, anchors[a]);
-    // kk pops of the workgroup's smallest remaining key, one barrier each (the two halves of s_red alternate).  The owner of the popped key
-    // moves on to its second key; only a thread that loses both re-reads its own anchors for the next one above the popped key.
+    const float2 gc = box_centre(gb);
+    unsigned long long k1 = kAtssNoKey, k2 = kAtssNoKey;   // the thread's two smallest keys
+    sweep_anchors<kAtssThreads>(anchors, a_begin, a_end, [&](int a, const float4& p) { keep_two<OpMinU64>(atss_key(p, gc, a), k1, k2); });
+    // kk pops of the workgroup's smallest remaining key.
     unsigned long long cur = k1, mine = kAtssNoKey, popped = 0ull;
     for (int j = 0; j < kk; ++j) {
-        const unsigned long long w = wave_allreduce(cur, OpMinU64());
-        if (lane == 0) s_red[j & 1][wave] = w;
-        __syncthreads();
-        popped = s_red[j & 1][0];
-#pragma unroll
-        for (int q = 1; q < kAtssWaves; ++q) { const unsigned long long t = s_red[j & 1][q]; popped = t < popped ? t : popped; }
+        popped = pop_first<OpMinU64, kAtssThreads>(cur, s_red, j);
         if (threadIdx.x == j) mine = popped;   // (kk <= 32: thread j keeps the j-th candidate)
-        if (cur == popped) {
-            if (cur == k1) cur = k2;   // (kAtssNoKey when the thread swept a single anchor: it has nothing left)
-            else {
-                cur = kAtssNoKey;
-                for (int b = a_begin + threadIdx.x; b < a_end; b += kAtssThreads) {
-                    const unsigned long long k = atss_key(anchors[b], gc, b);
-                    if (k > popped && k < cur) cur = k;
-                }
-            }
-        }
+        pop_advance(popped, cur, k1, k2, [&] {
+            return next_key_behind<OpMinU64, kAtssThreads>(popped, a_begin, a_end, [&](int b) { return atss_key(anchors[b], gc, b); });
+        });
     }
     if (threadIdx.x < kk) {   // rule 3's v_i, the IoU assign_kernel computes, in rank order
         const float4 c = to_corners(anchors[min((unsigned)(mine & 0xFFFFFFFFull), (unsigned)(a_end - 1))]);   // (a popped key is always an anchor of the level; the clamp costs nothing)
@@ -494,7 +560,7 @@ __global__ void __launch_bounds__(kAtssThreads) atss_candidates_kernel(const flo
 }
 
 __global__ void __launch_bounds__(kAssignThreads) atss_assign_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
-                                                                     const float4* __restrict__ anchors, int A, AtssLevels lv, int topk,
+                                                                     const float4* __restrict__ anchors, int A, Levels lv, int topk,
                                                                      const unsigned long long* __restrict__ cutoff, const float* __restrict__ cand_iou,
                                                                      float* __restrict__ target, int32_t* __restrict__ box_idx) {
     __shared__ float4 s_box[kGtChunk];
@@ -521,32 +587,34 @@ __global__ void __launch_bounds__(kAssignThreads) atss_assign_kernel(const float
     }
     float best = 0.0f;
     int bi = SSDK_NOT_MATCHED;
+    // for_box_chunks spelled out: beside the one-thread-per-box load, ALL threads of the block copy the chunk's n * L cutoffs together
+    // between the two barriers, which the helper's load functor has no place for.
     for (int base = 0; base < G; base += kGtChunk) {
         const int n = min(kGtChunk, G - base);
         __syncthreads();
         if (threadIdx.x < n) {
-            const int g = g0 + base + threadIdx.x;
+            const int j = threadIdx.x, g = g0 + base + j;
             const float* r = gt_rows + (size_t)g * gt_stride;
             const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
-            s_box[threadIdx.x] = gb;
-            s_area[threadIdx.x] = area4(gb.x, gb.y, gb.z, gb.w);
-            s_centre[threadIdx.x] = atss_centre(gb);
+            s_box[j] = gb;
+            s_area[j] = area4(gb.x, gb.y, gb.z, gb.w);
+            s_centre[j] = box_centre(gb);
             // t_g: fp64, two passes over the box's candidates in (level, rank) order -- the same order in every workgroup
             const float* v = cand_iou + (size_t)g * L * SSDK_ATSS_MAX_TOPK;
             double sum = 0.0;
             int cnt = 0;
             for (int q = 0; q < L; ++q) {
                 const int kk = min(topk, lv.off[q + 1] - lv.off[q]);
-                for (int j = 0; j < kk; ++j) sum += (double)v[q * SSDK_ATSS_MAX_TOPK + j];
+                for (int t = 0; t < kk; ++t) sum += (double)v[q * SSDK_ATSS_MAX_TOPK + t];
                 cnt += kk;
             }
             const double mean = sum / (double)cnt;
             double dev = 0.0;
             for (int q = 0; q < L; ++q) {
                 const int kk = min(topk, lv.off[q + 1] - lv.off[q]);
-                for (int j = 0; j < kk; ++j) { const double d = (double)v[q * SSDK_ATSS_MAX_TOPK + j] - mean; dev += d * d; }
+                for (int t = 0; t < kk; ++t) { const double d = (double)v[q * SSDK_ATSS_MAX_TOPK + t] - mean; dev += d * d; }
             }
-            s_thr[threadIdx.x] = (float)(mean + (cnt > 1 ? sqrt(dev / (double)(cnt - 1)) : 0.0));
+            s_thr[j] = (float)(mean + (cnt > 1 ? sqrt(dev / (double)(cnt - 1)) : 0.0));
         }
         for (int t = threadIdx.x; t < n * L; t += kAssignThreads) s_cut[t] = cutoff[(size_t)(g0 + base) * L + t];
         __syncthreads();
@@ -554,8 +622,7 @@ __global__ void __launch_bounds__(kAssignThreads) atss_assign_kernel(const float
             if (atss_key(p, s_centre[k], a) > s_cut[k * L + l]) continue;   // not among the box's nearest on this level
             const float4 gb = s_box[k];
             const float v = iou_corner(gb, s_area[k], c, carea);
-            const bool inside = gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w;
-            if (inside && v >= s_thr[k] && (bi < 0 || v > best)) { best = v; bi = base + k; }   // ascending k, strict >: the lowest box index keeps a tie
+            if (centre_inside(gb, p) && v >= s_thr[k] && (bi < 0 || v > best)) { best = v; bi = base + k; }   // ascending k, strict >: the lowest box index keeps a tie
         }
     }
     write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
@@ -594,8 +661,6 @@ __device__ __forceinline__ float tal_pow(float x, float e, bool six) {
     if (six && e == 6.0f) { const float x2 = x * x; return x2 * x2 * x2; }
     return __powf(x, e);
 }
-// column of the box's class in a row of logits, or -1 (rule 3: s = 0)
-__device__ __forceinline__ int tal_class_column(float cls, int C) { return (cls >= 1.0f && cls <= (float)C) ? (int)cls - 1 : -1; }
 // rules 1 - 3 and 5 for one (anchor, box): P the anchor's decoded corners, gb the box's, x the logit of the box's class (has_class: the class
 // is one of the columns).  Both launches call this, and decode_corners, on the same inputs: the same bits.
 __device__ __forceinline__ float tal_metric(float4 P, float4 gb, float x, bool has_class, const TalParams& tp, float& u) {
@@ -604,16 +669,6 @@ __device__ __forceinline__ float tal_metric(float4 P, float4 gb, float x, bool h
     return tal_pow(s, tp.alpha, false) * tal_pow(u, tp.beta, true);
 }
 __device__ __forceinline__ unsigned long long tal_key(float m, int a) { return make_key(ord_f32(m), a); }   // never 0: the low word is ~a >= 2^31
-__device__ __forceinline__ bool tal_inside(float4 gb, float4 p) { return gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w; }
-// image of row g (< gt_off[batch]): the last i with gt_off[i] <= g
-__device__ __forceinline__ int tal_image_of(const int32_t* __restrict__ gt_off, int batch, int g) {
-    int lo = 0, hi = batch - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (gt_off[mid] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ void __launch_bounds__(kTalThreads) tal_candidates_kernel(const float* __restrict__ gt_rows, int gt_stride, const int32_t* __restrict__ gt_off,
                                                                      int batch, const float4* __restrict__ anchors, int A,
@@ -623,11 +678,10 @@ __global__ void __launch_bounds__(kTalThreads) tal_candidates_kernel(const float
     __shared__ unsigned long long s_red[2][kTalWaves];
     const int g = blockIdx.x;
     if (g >= gt_off[batch]) return;   // rows past the last image's are padding (a row buffer of fixed capacity)
-    const int i = tal_image_of(gt_off, batch, g);
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const int i = image_of_row(gt_off, batch, g);
     const float* r = gt_rows + (size_t)g * gt_stride;
     const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
-    const int col = tal_class_column(r[4], tp.C);
+    const int col = class_column(r[4], tp.C);
     const size_t row0 = (size_t)i * A;
     auto metric = [&](int a, const float4& p, float& u) {   // of an inside anchor
         float4 cen;
@@ -635,51 +689,23 @@ __global__ void __launch_bounds__(kTalThreads) tal_candidates_kernel(const float
         const float x = col >= 0 ? scores[(row0 + a) * tp.C + col] : 0.0f;
         return tal_metric(P, gb, x, col >= 0, tp, u);
     };
-    // The sweep: the thread's two largest keys stay in registers (selects, as in atss_candidates_kernel).  0 = no key.
-    unsigned long long k1 = 0ull, k2 = 0ull;
-    auto take = [&](int a, const float4& p) {
+    auto key_of = [&](int a, const float4& p) {   // the inside test first; 0 = no key
         unsigned long long k = 0ull;
-        if (tal_inside(gb, p)) { float u; k = tal_key(metric(a, p, u), a); }
-        const bool gt1 = k > k1, gt2 = k > k2;
-        k2 = gt1 ? k1 : (gt2 ? k : k2);
-        k1 = gt1 ? k : k1;
+        if (centre_inside(gb, p)) { float u; k = tal_key(metric(a, p, u), a); }
+        return k;
     };
-    int a = threadIdx.x;
-    for (; a + 3 * kTalThreads < A; a += 4 * kTalThreads) {   // four loads in flight
-        const float4 p0 = anchors[a], p1 = anchors[a + kTalThreads], p2 = anchors[a + 2 * kTalThreads], p3 = anchors[a + 3 * kTalThreads];
-        take(a, p0);
-        take(a + kTalThreads, p1);
-        take(a + 2 * kTalThreads, p2);
-        take(a + 3 * kTalThreads, p3);
-    }
-    for (; a < A; a += kTalThreads) take(a, anchors[a]);
-    // Up to topk pops of the workgroup's largest remaining key, one barrier each (the two halves of s_red alternate); the first empty pop
-    // ends them: the box has fewer inside anchors than topk.  The owner of the popped key moves on to its second key; only a thread that
-    // loses both re-reads its own anchors for the next one below the popped key.
+    unsigned long long k1 = 0ull, k2 = 0ull;   // the thread's two largest keys
+    sweep_anchors<kTalThreads>(anchors, 0, A, [&](int a, const float4& p) { keep_two<OpMaxU64>(key_of(a, p), k1, k2); });
+    // Up to topk pops of the workgroup's largest remaining key; the first empty pop ends them: the box has fewer inside anchors than topk.
     unsigned long long cur = k1, mine = 0ull, last = kTalNoCutoff;
     for (int j = 0; j < topk; ++j) {
-        const unsigned long long w = wave_allreduce(cur, OpMaxU64());
-        if (lane == 0) s_red[j & 1][wave] = w;
-        __syncthreads();
-        unsigned long long popped = s_red[j & 1][0];
-#pragma unroll
-        for (int q = 1; q < kTalWaves; ++q) { const unsigned long long t = s_red[j & 1][q]; popped = t > popped ? t : popped; }
+        const unsigned long long popped = pop_first<OpMaxU64, kTalThreads>(cur, s_red, j);
         if (popped == 0ull) break;   // (the same value in every thread)
         last = popped;
         if (threadIdx.x == j) mine = popped;   // (topk <= 32: thread j keeps the j-th candidate)
-        if (cur == popped) {
-            if (cur == k1) cur = k2;   // (0 when the thread had a single inside anchor: it has nothing left)
-            else {
-                cur = 0ull;
-                for (int b = threadIdx.x; b < A; b += kTalThreads) {
-                    const float4 p = anchors[b];
-                    if (!tal_inside(gb, p)) continue;
-                    float u;
-                    const unsigned long long k = tal_key(metric(b, p, u), b);
-                    if (k < popped && k > cur) cur = k;
-                }
-            }
-        }
+        pop_advance(popped, cur, k1, k2, [&] {
+            return next_key_behind<OpMaxU64, kTalThreads>(popped, 0, A, [&](int b) { return key_of(b, anchors[b]); });
+        });
     }
     if (threadIdx.x < SSDK_TAL_MAX_TOPK) {   // the candidate list in rank order; the slots past kk say so
         const size_t slot = (size_t)g * SSDK_TAL_MAX_TOPK + threadIdx.x;
@@ -722,29 +748,24 @@ __global__ void __launch_bounds__(kAssignThreads) tal_assign_kernel(const float*
     }
     float best = 0.0f;
     int bi = SSDK_NOT_MATCHED;
-    for (int base = 0; base < G; base += kGtChunk) {
-        const int n = min(kGtChunk, G - base);
-        __syncthreads();
-        if (threadIdx.x < n) {
-            const int g = g0 + base + threadIdx.x;
-            const float* r = gt_rows + (size_t)g * gt_stride;
-            s_box[threadIdx.x] = make_float4(r[0], r[1], r[2], r[3]);
-            s_col[threadIdx.x] = tal_class_column(r[4], tp.C);
-            s_cut[threadIdx.x] = cutoff[g];
+    for_box_chunks(G, [&](int k, int j) {
+        const float* r = gt_rows + (size_t)(g0 + k) * gt_stride;
+        s_box[j] = make_float4(r[0], r[1], r[2], r[3]);
+        s_col[j] = class_column(r[4], tp.C);
+        s_cut[j] = cutoff[g0 + k];
+    }, [&](int base, int n) {
+        if (!live) return;
+        for (int k = 0; k < n; ++k) {
+            const float4 gb = s_box[k];
+            if (!centre_inside(gb, p)) continue;
+            const int col = s_col[k];
+            const float x = col >= 0 ? scores[row * tp.C + col] : 0.0f;
+            float u;
+            const float m = tal_metric(P, gb, x, col >= 0, tp, u);
+            if (tal_key(m, a) < s_cut[k]) continue;                      // not among the box's topk
+            if (bi < 0 || u > best) { best = u; bi = base + k; }         // rule 7: ascending k, strict >: the lowest box index keeps a tie
         }
-        __syncthreads();
-        if (live)
-            for (int k = 0; k < n; ++k) {
-                const float4 gb = s_box[k];
-                if (!tal_inside(gb, p)) continue;
-                const int col = s_col[k];
-                const float x = col >= 0 ? scores[row * tp.C + col] : 0.0f;
-                float u;
-                const float m = tal_metric(P, gb, x, col >= 0, tp, u);
-                if (tal_key(m, a) < s_cut[k]) continue;                      // not among the box's topk
-                if (bi < 0 || u > best) { best = u; bi = base + k; }         // rule 7: ascending k, strict >: the lowest box index keeps a tie
-            }
-    }
+    });
     if (bi >= 0) {   // the thread is one of its box's candidates: its slot in the box's list (at most 32 entries, positives only)
         const size_t slot0 = (size_t)(g0 + bi) * SSDK_TAL_MAX_TOPK;
         for (int j = 0; j < SSDK_TAL_MAX_TOPK; ++j)
@@ -760,7 +781,7 @@ __global__ void __launch_bounds__(kTalNormThreads) tal_normalise_kernel(const fl
     const int g = blockIdx.x * (kTalNormThreads / kWave) + (threadIdx.x >> 6);
     if (g >= gt_off[batch]) return;   // (a whole wave leaves: no barrier in this kernel)
     const int lane = lane_id();
-    const int i = tal_image_of(gt_off, batch, g);
+    const int i = image_of_row(gt_off, batch, g);
     const size_t slot = (size_t)g * SSDK_TAL_MAX_TOPK + (lane < SSDK_TAL_MAX_TOPK ? lane : 0);
     const int a = lane < SSDK_TAL_MAX_TOPK ? cand_anchor[slot] : -1;
     const bool kept = a >= 0 && cand_kept[slot] != 0;
@@ -795,24 +816,24 @@ __global__ void __launch_bounds__(kTalNormThreads) tal_normalise_kernel(const fl
 constexpr int kSimotaThreads = 1024;
 constexpr int kSimotaWaves = kSimotaThreads / kWave;
 constexpr unsigned long long kSimotaNoKey = ~0ull;   // above every cost-key (an anchor index is below 2^31 - 1)
-// by value: level l owns anchors [off[l], off[l + 1]) (the entries past n repeat the total) and has the centre square's half sides
-// (rx, ry) = center_radius * (sx, sy), one fp32 product each, formed on the host
-struct SimotaLevels { int n; int off[SSDK_ATSS_MAX_LEVELS + 1]; float rx[SSDK_ATSS_MAX_LEVELS]; float ry[SSDK_ATSS_MAX_LEVELS]; };
+// by value: beside the level table, every level's centre square's half sides (rx, ry) = center_radius * (sx, sy), one fp32 product each,
+// formed on the host
+struct SimotaLevels { Levels lv; float rx[SSDK_ATSS_MAX_LEVELS]; float ry[SSDK_ATSS_MAX_LEVELS]; };
 struct SimotaParams { float xy_scale, wh_scale, iou_weight; int C; };
 
 // (rx, ry) of anchor a's level (constant indices: a by-value table indexed by a variable would be copied to scratch)
-__device__ __forceinline__ float2 simota_radius(const SimotaLevels& lv, int a) {
-    float2 r = make_float2(lv.rx[0], lv.ry[0]);
+__device__ __forceinline__ float2 simota_radius(const SimotaLevels& sl, int a) {
+    float2 r = make_float2(sl.rx[0], sl.ry[0]);
 #pragma unroll
     for (int q = 1; q < SSDK_ATSS_MAX_LEVELS; ++q) {
-        if (q >= lv.n) break;   // (the same in every lane: a scalar branch past the levels that do not exist)
-        if (a >= lv.off[q]) r = make_float2(lv.rx[q], lv.ry[q]);
+        if (q >= sl.lv.n) break;   // (the same in every lane: a scalar branch past the levels that do not exist)
+        if (a >= sl.lv.off[q]) r = make_float2(sl.rx[q], sl.ry[q]);
     }
     return r;
 }
-// rule 2 on the inputs: exact.  gc = atss_centre(gb), r = simota_radius(level of p)
+// rule 2 on the inputs: exact.  gc = box_centre(gb), r = simota_radius(level of p)
 __device__ __forceinline__ bool simota_region(float4 gb, float2 gc, float4 p, float2 r, bool& penalised) {
-    const bool in_box = gb.x < p.x && p.x < gb.z && gb.y < p.y && p.y < gb.w;
+    const bool in_box = centre_inside(gb, p);
     const bool in_centre = gc.x - r.x < p.x && p.x < gc.x + r.x && gc.y - r.y < p.y && p.y < gc.y + r.y;
     penalised = !(in_box && in_centre);
     return in_box || in_centre;
@@ -869,22 +890,18 @@ __global__ void __launch_bounds__(kAssignThreads) simota_class_sum_kernel(const 
         r = simota_radius(lv, a);
     }
     bool hit = false;   // the anchor lies in some box's region
-    for (int base = 0; base < G; base += kGtChunk) {
-        const int n = min(kGtChunk, G - base);
-        __syncthreads();
-        if (threadIdx.x < n) {
-            const float* row = gt_rows + (size_t)(g0 + base + threadIdx.x) * gt_stride;
-            const float4 gb = make_float4(row[0], row[1], row[2], row[3]);
-            s_box[threadIdx.x] = gb;
-            s_centre[threadIdx.x] = atss_centre(gb);
-        }
-        __syncthreads();
+    for_box_chunks(G, [&](int k, int j) {
+        const float* row = gt_rows + (size_t)(g0 + k) * gt_stride;
+        const float4 gb = make_float4(row[0], row[1], row[2], row[3]);
+        s_box[j] = gb;
+        s_centre[j] = box_centre(gb);
+    }, [&](int base, int n) {
         if (live && !hit)
             for (int k = 0; k < n; ++k) {
                 bool pen;
                 if (simota_region(s_box[k], s_centre[k], p, r, pen)) { hit = true; break; }
             }
-    }
+    });
     // The block's region anchors, in anchor order, into s_rows (ballot + popcount: no atomics); then eight lanes per row, so that a row of
     // logits is read as whole 128-byte runs instead of one 16-byte piece per lane and row.
     const int lane = lane_id(), wave = threadIdx.x >> 6;
@@ -923,16 +940,15 @@ __global__ void __launch_bounds__(kSimotaThreads) simota_candidates_kernel(const
         if (dynamic_k && threadIdx.x == 0) dynamic_k[g] = 0;
         return;
     }
-    const int i = tal_image_of(gt_off, batch, g);
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const int i = image_of_row(gt_off, batch, g);
     const float* r = gt_rows + (size_t)g * gt_stride;
     const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
-    const float2 gc = atss_centre(gb);
-    const int col = tal_class_column(r[4], sp.C);
+    const float2 gc = box_centre(gb);
+    const int col = class_column(r[4], sp.C);
     const size_t row0 = (size_t)i * A;
     // An anchor against the box in two steps, so that a sweep round can have the gathered loads of its four anchors in flight together:
     // `fetch` is the region test and, for a region anchor, the loads of its loc, class sum and the one logit of the box's class; `finish`
-    // turns what was fetched into the two keys.
+    // turns what was fetched into the two keys (and leaves them as they were for an anchor outside the region).
     struct Fetched { float4 t; float x, S; bool in, pen; };
     auto fetch = [&](int a, const float4& p, Fetched& f) {
         f.in = simota_region(gb, gc, p, simota_radius(lv, a), f.pen);
@@ -943,34 +959,20 @@ __global__ void __launch_bounds__(kSimotaThreads) simota_candidates_kernel(const
         }
     };
     auto finish = [&](int a, const float4& p, const Fetched& f, unsigned long long& ku, unsigned long long& kc) {
-        if (!f.in) return false;
+        if (!f.in) return;
         float4 cen;
         const float4 P = decode_corners(f.t, p, sp.xy_scale, sp.wh_scale, cen);
         const float u = box_quality(P, gb);
         ku = make_key(ord_f32(u), a);   // never 0: the low word is ~a >= 2^31
         kc = simota_key(f.pen, simota_cost(f.S, f.x, col >= 0, u, sp.iou_weight), a);
-        return true;
     };
-    auto keys = [&](int a, const float4& p, unsigned long long& ku, unsigned long long& kc) {
-        Fetched f;
-        fetch(a, p, f);
-        return finish(a, p, f, ku, kc);
-    };
-    // The sweep: the thread's two largest u-keys (0 = none) and two smallest cost-keys (kSimotaNoKey = none) stay in registers (selects,
-    // as in atss_candidates_kernel).
+    // The sweep: the thread's two largest u-keys (0 = none) and two smallest cost-keys (kSimotaNoKey = none).
     unsigned long long u1 = 0ull, u2 = 0ull, c1 = kSimotaNoKey, c2 = kSimotaNoKey;
-    auto keep = [&](unsigned long long ku, unsigned long long kc) {
-        const bool gt1 = ku > u1, gt2 = ku > u2;
-        u2 = gt1 ? u1 : (gt2 ? ku : u2);
-        u1 = gt1 ? ku : u1;
-        const bool lt1 = kc < c1, lt2 = kc < c2;
-        c2 = lt1 ? c1 : (lt2 ? kc : c2);
-        c1 = lt1 ? kc : c1;
-    };
     auto take = [&](int a, const float4& p, const Fetched& f) {
         unsigned long long ku = 0ull, kc = kSimotaNoKey;
         finish(a, p, f, ku, kc);
-        keep(ku, kc);
+        keep_two<OpMaxU64>(ku, u1, u2);
+        keep_two<OpMinU64>(kc, c1, c2);
     };
     int a = threadIdx.x;
     for (; a + 3 * kSimotaThreads < A; a += 4 * kSimotaThreads) {   // four anchor loads in flight, then the four anchors' gathered loads
@@ -991,56 +993,40 @@ __global__ void __launch_bounds__(kSimotaThreads) simota_candidates_kernel(const
         fetch(a, p, f);
         take(a, p, f);
     }
-    // Rule 5: up to topk pops of the workgroup's largest remaining u-key, one barrier each (the two halves of s_red alternate over BOTH pop
-    // loops); the first empty pop ends them: the box has fewer region anchors than topk.  Every thread adds the popped u to its own copy of
-    // the sum, in rank order.  The owner of a popped key moves on to its second key; a thread that loses both re-reads its own anchors.
+    // A re-read of the thread's own anchors: anchor b's u-key (want_u) or cost-key, `none` outside the region.
+    auto key_of = [&](int b, bool want_u) {
+        const float4 p = anchors[b];
+        Fetched f;
+        fetch(b, p, f);
+        unsigned long long ku = 0ull, kc = kSimotaNoKey;
+        finish(b, p, f, ku, kc);
+        return want_u ? ku : kc;
+    };
+    // Rule 5: up to topk pops of the workgroup's largest remaining u-key (`step` counts the pops of BOTH loops: they share s_red's
+    // halves); the first empty pop ends them: the box has fewer region anchors than topk.  Every thread adds the popped u to its own copy
+    // of the sum, in rank order.
     int step = 0, qq = 0;
     double sum = 0.0;
     unsigned long long cur = u1;
-    for (int j = 0; j < topk; ++j, ++step) {
-        const unsigned long long w = wave_allreduce(cur, OpMaxU64());
-        if (lane == 0) s_red[step & 1][wave] = w;
-        __syncthreads();
-        unsigned long long popped = s_red[step & 1][0];
-#pragma unroll
-        for (int q = 1; q < kSimotaWaves; ++q) { const unsigned long long t = s_red[step & 1][q]; popped = t > popped ? t : popped; }
-        if (popped == 0ull) { ++step; break; }   // (the same value in every thread)
+    for (int j = 0; j < topk; ++j) {
+        const unsigned long long popped = pop_first<OpMaxU64, kSimotaThreads>(cur, s_red, step++);
+        if (popped == 0ull) break;   // (the same value in every thread)
         ++qq;
         sum += (double)__uint_as_float(key_hi(popped) & 0x7FFFFFFFu);   // u >= 0: ord_f32 set the sign bit, 0 is kOrdZero
-        if (cur == popped) {
-            if (cur == u1) cur = u2;
-            else {
-                cur = 0ull;
-                for (int b = threadIdx.x; b < A; b += kSimotaThreads) {
-                    unsigned long long ku, kc;
-                    if (keys(b, anchors[b], ku, kc) && ku < popped && ku > cur) cur = ku;
-                }
-            }
-        }
+        pop_advance(popped, cur, u1, u2, [&] {
+            return next_key_behind<OpMaxU64, kSimotaThreads>(popped, 0, A, [&](int b) { return key_of(b, true); });
+        });
     }
     int kg = 0;
     if (qq > 0) kg = min(max((int)sum, 1), qq);   // (sum <= 32)
     // Rule 6: kg pops of the smallest remaining cost-key; the last is the box's cutoff.  kg <= #region: no pop is empty.
     unsigned long long last = 0ull;   // below every key: a box without a region anchor has no candidate
     cur = c1;
-    for (int j = 0; j < kg; ++j, ++step) {
-        const unsigned long long w = wave_allreduce(cur, OpMinU64());
-        if (lane == 0) s_red[step & 1][wave] = w;
-        __syncthreads();
-        unsigned long long popped = s_red[step & 1][0];
-#pragma unroll
-        for (int q = 1; q < kSimotaWaves; ++q) { const unsigned long long t = s_red[step & 1][q]; popped = t < popped ? t : popped; }
-        last = popped;
-        if (cur == popped) {
-            if (cur == c1) cur = c2;
-            else {
-                cur = kSimotaNoKey;
-                for (int b = threadIdx.x; b < A; b += kSimotaThreads) {
-                    unsigned long long ku, kc;
-                    if (keys(b, anchors[b], ku, kc) && kc > popped && kc < cur) cur = kc;
-                }
-            }
-        }
+    for (int j = 0; j < kg; ++j) {
+        last = pop_first<OpMinU64, kSimotaThreads>(cur, s_red, step++);
+        pop_advance(last, cur, c1, c2, [&] {
+            return next_key_behind<OpMinU64, kSimotaThreads>(last, 0, A, [&](int b) { return key_of(b, false); });
+        });
     }
     if (threadIdx.x == 0) {
         cutoff[g] = last;
@@ -1079,34 +1065,29 @@ __global__ void __launch_bounds__(kAssignThreads) simota_assign_kernel(const flo
     bool have_S = false;   // (launch 1 stored S only where some box's region holds the anchor: read it on the first hit)
     unsigned long long best = 0ull;
     int bi = SSDK_NOT_MATCHED;
-    for (int base = 0; base < G; base += kGtChunk) {
-        const int n = min(kGtChunk, G - base);
-        __syncthreads();
-        if (threadIdx.x < n) {
-            const int g = g0 + base + threadIdx.x;
-            const float* r = gt_rows + (size_t)g * gt_stride;
-            const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
-            s_box[threadIdx.x] = gb;
-            s_centre[threadIdx.x] = atss_centre(gb);
-            s_col[threadIdx.x] = tal_class_column(r[4], sp.C);
-            s_cut[threadIdx.x] = cutoff[g];
+    for_box_chunks(G, [&](int k, int j) {
+        const float* r = gt_rows + (size_t)(g0 + k) * gt_stride;
+        const float4 gb = make_float4(r[0], r[1], r[2], r[3]);
+        s_box[j] = gb;
+        s_centre[j] = box_centre(gb);
+        s_col[j] = class_column(r[4], sp.C);
+        s_cut[j] = cutoff[g0 + k];
+    }, [&](int base, int n) {
+        if (!live) return;
+        for (int k = 0; k < n; ++k) {
+            const float4 gb = s_box[k];
+            bool pen;
+            if (!simota_region(gb, s_centre[k], p, rad, pen)) continue;
+            if (!have_S) { S = class_sum[row]; have_S = true; }
+            const int col = s_col[k];
+            const float x = col >= 0 ? scores[row * sp.C + col] : 0.0f;
+            const float u = box_quality(P, gb);
+            const unsigned long long key = simota_key(pen, simota_cost(S, x, col >= 0, u, sp.iou_weight), a);
+            if (key > s_cut[k]) continue;                                           // not among the box's k_g
+            const unsigned long long rank = key >> 31;                              // rule 7: (penalised, cost) without the anchor
+            if (bi < 0 || rank < best) { best = rank; bi = base + k; }              // ascending k, strict <: the lowest box index keeps a tie
         }
-        __syncthreads();
-        if (live)
-            for (int k = 0; k < n; ++k) {
-                const float4 gb = s_box[k];
-                bool pen;
-                if (!simota_region(gb, s_centre[k], p, rad, pen)) continue;
-                if (!have_S) { S = class_sum[row]; have_S = true; }
-                const int col = s_col[k];
-                const float x = col >= 0 ? scores[row * sp.C + col] : 0.0f;
-                const float u = box_quality(P, gb);
-                const unsigned long long key = simota_key(pen, simota_cost(S, x, col >= 0, u, sp.iou_weight), a);
-                if (key > s_cut[k]) continue;                                           // not among the box's k_g
-                const unsigned long long rank = key >> 31;                              // rule 7: (penalised, cost) without the anchor
-                if (bi < 0 || rank < best) { best = rank; bi = base + k; }              // ascending k, strict <: the lowest box index keeps a tie
-            }
-    }
+    });
     write_target_rows(gt_rows, gt_stride, g0, bi, i, a0, A, s_out, target, box_idx);
 }
 
@@ -1144,41 +1125,6 @@ extern "C" int ssdk_match_per_prediction(const float* weights, int num_boxes, in
     return SSDK_OK;
 }
 
-extern "C" size_t ssdk_encode_ground_truth_workspace_bytes(int batch, int total_gt) {
-    (void)batch;
-    Carver c(nullptr);
-    c.take<unsigned long long>((size_t)(total_gt > 0 ? total_gt : 1) * kArgmaxMaxSegs);
-    return c.off;
-}
-
-extern "C" int ssdk_encode_ground_truth(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch,
-                                        int total_gt, const float* anchors, int num_anchors, float matched_threshold,
-                                        float unmatched_threshold, float* target, int32_t* box_idx, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
-    SSDK_REQUIRE(batch <= 65535 && total_gt <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth: batch/total_gt exceed grid limits");
-    SSDK_REQUIRE(gt_offsets && anchors && target && (gt_rows || total_gt == 0), SSDK_E_INVALID, "ssdk_encode_ground_truth: null pointer");
-    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth: gt_stride=%d < 6", gt_stride);
-    SSDK_REQUIRE(matched_threshold >= unmatched_threshold, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth: matched_threshold < unmatched_threshold (matcher.py:43)");
-    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_workspace_bytes(batch, total_gt), SSDK_E_WORKSPACE,
-                 "ssdk_encode_ground_truth: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    Carver c(workspace);
-    unsigned long long* gt_best = c.take<unsigned long long>((size_t)(total_gt > 0 ? total_gt : 1) * kArgmaxMaxSegs);
-    const int segs = argmax_segs(num_anchors);
-    if (total_gt > 0) {
-        hipLaunchKernelGGL(gt_argmax_kernel, dim3(total_gt, segs), dim3(kArgmaxThreads), 0, s, gt_rows, gt_stride, (const float4*)anchors, num_anchors, gt_best, gt_offsets, batch);
-        SSDK_CHECK_LAUNCH("gt_argmax_kernel");
-    }
-    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
-    hipLaunchKernelGGL(assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
-                       num_anchors, matched_threshold, unmatched_threshold, gt_best, segs, target, box_idx);
-    SSDK_CHECK_LAUNCH("assign_kernel");
-    return SSDK_OK;
-}
-
 extern "C" size_t ssdk_match_bipartite_workspace_bytes(int num_boxes, int num_anchors) {
     const size_t g = (size_t)(num_boxes > 0 ? num_boxes : 1), a = (size_t)(num_anchors > 0 ? num_anchors : 1);
     Carver c(nullptr);
@@ -1212,14 +1158,115 @@ extern "C" int ssdk_match_bipartite(float* weights, int num_boxes, int num_ancho
     return SSDK_OK;
 }
 
-extern "C" size_t ssdk_encode_ground_truth_ex_workspace_bytes(int batch, int total_gt, int force_match) {
-    Carver c(nullptr);
-    c.off = ssdk_encode_ground_truth_workspace_bytes(batch, total_gt);
-    if (force_match == SSDK_FORCE_MATCH_BIPARTITE) {
-        c.take<unsigned long long>((size_t)(total_gt > 0 ? total_gt : 1));
-        c.take<int>((size_t)(total_gt > 0 ? total_gt : 1));
+// ---- the ssdk_encode_ground_truth* entry points -------------------------------------------------------------------------------------------
+// What they all require, under the entry's own name.  `further_ptrs`: the entry's further mandatory pointers are there;
+// `total_gt_limit`: the two IoU entries also bound total_gt.
+constexpr bool kNoFurtherPointers = true;
+enum TotalGtLimit { kBatchLimitOnly, kBatchAndTotalGtLimit };
+static int check_encode_args(const char* entry, const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                             const float* anchors, int num_anchors, const float* target, bool further_ptrs, TotalGtLimit total_gt_limit) {
+    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID, "%s: batch=%d anchors=%d total_gt=%d", entry, batch, num_anchors,
+                 total_gt);
+    if (total_gt_limit == kBatchAndTotalGtLimit)
+        SSDK_REQUIRE(batch <= 65535 && total_gt <= 65535, SSDK_E_INVALID, "%s: batch/total_gt exceed grid limits", entry);
+    else
+        SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "%s: batch exceeds grid limits", entry);
+    SSDK_REQUIRE(gt_offsets && anchors && target && further_ptrs && (gt_rows || total_gt == 0), SSDK_E_INVALID, "%s: null pointer", entry);
+    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "%s: gt_stride=%d < 6", entry, gt_stride);
+    return SSDK_OK;
+}
+// The last check of every entry, after its own arguments are known to be valid: `need` is the entry's carve of the workspace.
+static int check_workspace(const char* entry, const void* workspace, size_t workspace_bytes, size_t need) {
+    SSDK_REQUIRE(workspace && workspace_bytes >= need, SSDK_E_WORKSPACE, "%s: workspace too small", entry);
+    return SSDK_OK;
+}
+// What the two prediction-aware entries (TAL, SimOTA) require of the anchors' own predictions.
+static int check_prediction_args(const char* entry, const float* anchors, const float* scores, int num_columns, const float* locs) {
+    SSDK_REQUIRE(scores && locs, SSDK_E_INVALID, "%s: null scores or locs (the rule reads the anchors' own predictions)", entry);
+    SSDK_REQUIRE(num_columns >= 1, SSDK_E_INVALID, "%s: num_columns=%d < 1", entry, num_columns);
+    SSDK_REQUIRE((((uintptr_t)anchors | (uintptr_t)locs) & 15) == 0, SSDK_E_UNSUPPORTED, "%s: anchors and locs must be 16-byte aligned", entry);
+    return SSDK_OK;
+}
+// The by-value level table of ATSS and SimOTA from the caller's level sizes, which must be positive and sum to the anchors.
+static int build_levels(const char* entry, const int32_t* level_sizes, int n_levels, int num_anchors, Levels& lv) {
+    SSDK_REQUIRE(n_levels >= 1 && n_levels <= SSDK_ATSS_MAX_LEVELS, SSDK_E_INVALID, "%s: n_levels=%d outside 1..%d", entry, n_levels,
+                 SSDK_ATSS_MAX_LEVELS);
+    lv.n = n_levels;
+    long long sum = 0;
+    for (int l = 0; l <= SSDK_ATSS_MAX_LEVELS; ++l) {
+        lv.off[l] = (int)sum;   // (the entries past n_levels repeat the total)
+        if (l < n_levels) {
+            SSDK_REQUIRE(level_sizes[l] > 0, SSDK_E_INVALID, "%s: level_sizes[%d]=%d", entry, l, level_sizes[l]);
+            sum += level_sizes[l];
+            SSDK_REQUIRE(sum <= num_anchors, SSDK_E_INVALID, "%s: level sizes exceed the %d anchors", entry, num_anchors);
+        }
     }
-    return c.off;
+    SSDK_REQUIRE(sum == num_anchors, SSDK_E_INVALID, "%s: level sizes sum to %lld, not to the %d anchors", entry, sum, num_anchors);
+    return SSDK_OK;
+}
+static inline size_t box_slots(int total_gt) { return (size_t)(total_gt > 0 ? total_gt : 1); }
+
+// Every workspace is carved by ONE function: *_workspace_bytes calls it on a null base for `bytes`, the entry point on the workspace.
+struct IouWorkspace { unsigned long long* gt_best; unsigned long long* spill_keys; int* spill_rows; size_t bytes; };
+static IouWorkspace carve_iou(void* base, int total_gt, int force_match) {
+    Carver c(base);
+    IouWorkspace w = {};
+    w.gt_best = c.take<unsigned long long>(box_slots(total_gt) * kArgmaxMaxSegs);
+    if (force_match == SSDK_FORCE_MATCH_BIPARTITE) {
+        w.spill_keys = c.take<unsigned long long>(box_slots(total_gt));
+        w.spill_rows = c.take<int>(box_slots(total_gt));
+    }
+    w.bytes = c.off;
+    return w;
+}
+
+extern "C" size_t ssdk_encode_ground_truth_workspace_bytes(int batch, int total_gt) {
+    (void)batch;
+    return carve_iou(nullptr, total_gt, SSDK_FORCE_MATCH_PER_PREDICTION).bytes;
+}
+
+extern "C" size_t ssdk_encode_ground_truth_ex_workspace_bytes(int batch, int total_gt, int force_match) {
+    (void)batch;
+    return carve_iou(nullptr, total_gt, force_match).bytes;
+}
+
+// Both IoU entry points: gt_argmax_kernel, the bipartite stage where asked for, assign_kernel.
+static int encode_iou(const char* entry, const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
+                      const float* anchors, int num_anchors, float matched_threshold, float unmatched_threshold, int force_match, float* target,
+                      int32_t* box_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    const bool bipartite = force_match == SSDK_FORCE_MATCH_BIPARTITE;
+    const IouWorkspace w = carve_iou(workspace, total_gt, force_match);
+    int e = check_encode_args(entry, gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, target, kNoFurtherPointers,
+                              kBatchAndTotalGtLimit);
+    if (e != SSDK_OK) return e;
+    SSDK_REQUIRE(!bipartite || num_anchors <= kBipMaxAnchors, SSDK_E_UNSUPPORTED, "%s: bipartite matching takes at most %d anchors, got %d", entry,
+                 kBipMaxAnchors, num_anchors);
+    SSDK_REQUIRE(matched_threshold >= unmatched_threshold, SSDK_E_INVALID, "%s: matched_threshold < unmatched_threshold (matcher.py:43)", entry);
+    if ((e = check_workspace(entry, workspace, workspace_bytes, w.bytes)) != SSDK_OK) return e;
+    hipStream_t s = (hipStream_t)stream;
+    const int segs = argmax_segs(num_anchors);
+    if (total_gt > 0) {
+        hipLaunchKernelGGL(gt_argmax_kernel, dim3(total_gt, segs), dim3(kArgmaxThreads), 0, s, gt_rows, gt_stride, (const float4*)anchors, num_anchors, w.gt_best, gt_offsets, batch);
+        SSDK_CHECK_LAUNCH("gt_argmax_kernel");
+        if (bipartite) {
+            hipLaunchKernelGGL(bipartite_resolve_kernel, dim3(batch), dim3(kBipThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
+                               num_anchors, w.gt_best, segs, w.spill_keys, w.spill_rows);
+            SSDK_CHECK_LAUNCH("bipartite_resolve_kernel");
+        }
+    }
+    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
+    hipLaunchKernelGGL(assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
+                       num_anchors, matched_threshold, unmatched_threshold, w.gt_best, segs, target, box_idx);
+    SSDK_CHECK_LAUNCH("assign_kernel");
+    return SSDK_OK;
+}
+
+extern "C" int ssdk_encode_ground_truth(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch,
+                                        int total_gt, const float* anchors, int num_anchors, float matched_threshold,
+                                        float unmatched_threshold, float* target, int32_t* box_idx, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    return encode_iou("ssdk_encode_ground_truth", gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, matched_threshold,
+                      unmatched_threshold, SSDK_FORCE_MATCH_PER_PREDICTION, target, box_idx, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ssdk_encode_ground_truth_ex(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
@@ -1228,162 +1275,122 @@ extern "C" int ssdk_encode_ground_truth_ex(const float* gt_rows, int gt_stride, 
                                            void* stream) {
     SSDK_REQUIRE(force_match == SSDK_FORCE_MATCH_PER_PREDICTION || force_match == SSDK_FORCE_MATCH_BIPARTITE, SSDK_E_INVALID,
                  "ssdk_encode_ground_truth_ex: force_match=%d", force_match);
-    if (force_match == SSDK_FORCE_MATCH_PER_PREDICTION)
-        return ssdk_encode_ground_truth(gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, matched_threshold,
-                                        unmatched_threshold, target, box_idx, workspace, workspace_bytes, stream);
-    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_ex: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
-    SSDK_REQUIRE(batch <= 65535 && total_gt <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_ex: batch/total_gt exceed grid limits");
-    SSDK_REQUIRE(num_anchors <= kBipMaxAnchors, SSDK_E_UNSUPPORTED, "ssdk_encode_ground_truth_ex: bipartite matching takes at most %d anchors, got %d",
-                 kBipMaxAnchors, num_anchors);
-    SSDK_REQUIRE(gt_offsets && anchors && target && (gt_rows || total_gt == 0), SSDK_E_INVALID, "ssdk_encode_ground_truth_ex: null pointer");
-    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_ex: gt_stride=%d < 6", gt_stride);
-    SSDK_REQUIRE(matched_threshold >= unmatched_threshold, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_ex: matched_threshold < unmatched_threshold (matcher.py:43)");
-    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_ex_workspace_bytes(batch, total_gt, force_match), SSDK_E_WORKSPACE,
-                 "ssdk_encode_ground_truth_ex: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t slots = (size_t)(total_gt > 0 ? total_gt : 1);
-    Carver c(workspace);
-    unsigned long long* gt_best = c.take<unsigned long long>(slots * kArgmaxMaxSegs);
-    unsigned long long* spill_keys = c.take<unsigned long long>(slots);
-    int* spill_rows = c.take<int>(slots);
-    const int segs = argmax_segs(num_anchors);
-    if (total_gt > 0) {
-        hipLaunchKernelGGL(gt_argmax_kernel, dim3(total_gt, segs), dim3(kArgmaxThreads), 0, s, gt_rows, gt_stride, (const float4*)anchors, num_anchors, gt_best, gt_offsets, batch);
-        SSDK_CHECK_LAUNCH("gt_argmax_kernel");
-        hipLaunchKernelGGL(bipartite_resolve_kernel, dim3(batch), dim3(kBipThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors,
-                           gt_best, segs, spill_keys, spill_rows);
-        SSDK_CHECK_LAUNCH("bipartite_resolve_kernel");
-    }
-    dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
-    hipLaunchKernelGGL(assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
-                       num_anchors, matched_threshold, unmatched_threshold, gt_best, segs, target, box_idx);
-    SSDK_CHECK_LAUNCH("assign_kernel");
-    return SSDK_OK;
+    // (the default rule keeps the messages it always had: ssdk_encode_ground_truth's)
+    return encode_iou(force_match == SSDK_FORCE_MATCH_BIPARTITE ? "ssdk_encode_ground_truth_ex" : "ssdk_encode_ground_truth", gt_rows, gt_stride,
+                      gt_offsets, batch, total_gt, anchors, num_anchors, matched_threshold, unmatched_threshold, force_match, target, box_idx,
+                      workspace, workspace_bytes, stream);
+}
+
+struct AtssWorkspace { unsigned long long* cutoff; float* cand_iou; size_t bytes; };
+static AtssWorkspace carve_atss(void* base, int total_gt, int n_levels) {
+    const size_t slots = box_slots(total_gt) * (size_t)(n_levels > 0 ? n_levels : 1);
+    Carver c(base);
+    AtssWorkspace w;
+    w.cutoff = c.take<unsigned long long>(slots);
+    w.cand_iou = c.take<float>(slots * SSDK_ATSS_MAX_TOPK);
+    w.bytes = c.off;
+    return w;
 }
 
 extern "C" size_t ssdk_encode_ground_truth_atss_workspace_bytes(int batch, int total_gt, int n_levels) {
     (void)batch;
-    const size_t slots = (size_t)(total_gt > 0 ? total_gt : 1) * (size_t)(n_levels > 0 ? n_levels : 1);
-    Carver c(nullptr);
-    c.take<unsigned long long>(slots);
-    c.take<float>(slots * SSDK_ATSS_MAX_TOPK);
-    return c.off;
+    return carve_atss(nullptr, total_gt, n_levels).bytes;
 }
 
 extern "C" int ssdk_encode_ground_truth_atss(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
                                              const float* anchors, int num_anchors, const int32_t* level_sizes, int n_levels, int topk,
                                              float* target, int32_t* box_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_atss: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
-    SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: batch exceeds grid limits");
-    SSDK_REQUIRE(gt_offsets && anchors && target && level_sizes && (gt_rows || total_gt == 0), SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_atss: null pointer");
-    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: gt_stride=%d < 6", gt_stride);
-    SSDK_REQUIRE(n_levels >= 1 && n_levels <= SSDK_ATSS_MAX_LEVELS, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: n_levels=%d outside 1..%d",
-                 n_levels, SSDK_ATSS_MAX_LEVELS);
-    SSDK_REQUIRE(topk >= 1 && topk <= SSDK_ATSS_MAX_TOPK, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: topk=%d outside 1..%d", topk,
-                 SSDK_ATSS_MAX_TOPK);
-    AtssLevels lv;
-    lv.n = n_levels;
-    long long sum = 0;
-    for (int l = 0; l <= SSDK_ATSS_MAX_LEVELS; ++l) {
-        lv.off[l] = (int)sum;   // (the entries past n_levels repeat the total)
-        if (l < n_levels) {
-            SSDK_REQUIRE(level_sizes[l] > 0, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: level_sizes[%d]=%d", l, level_sizes[l]);
-            sum += level_sizes[l];
-            SSDK_REQUIRE(sum <= num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: level sizes exceed the %d anchors", num_anchors);
-        }
-    }
-    SSDK_REQUIRE(sum == num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_atss: level sizes sum to %lld, not to the %d anchors", sum,
-                 num_anchors);
-    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_atss_workspace_bytes(batch, total_gt, n_levels), SSDK_E_WORKSPACE,
-                 "ssdk_encode_ground_truth_atss: workspace too small");
+    const char* entry = "ssdk_encode_ground_truth_atss";
+    const AtssWorkspace w = carve_atss(workspace, total_gt, n_levels);
+    int e = check_encode_args(entry, gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, target, level_sizes != nullptr,
+                              kBatchLimitOnly);
+    if (e != SSDK_OK) return e;
+    Levels lv;
+    if ((e = build_levels(entry, level_sizes, n_levels, num_anchors, lv)) != SSDK_OK) return e;
+    SSDK_REQUIRE(topk >= 1 && topk <= SSDK_ATSS_MAX_TOPK, SSDK_E_INVALID, "%s: topk=%d outside 1..%d", entry, topk, SSDK_ATSS_MAX_TOPK);
+    if ((e = check_workspace(entry, workspace, workspace_bytes, w.bytes)) != SSDK_OK) return e;
     hipStream_t s = (hipStream_t)stream;
-    const size_t slots = (size_t)(total_gt > 0 ? total_gt : 1) * (size_t)n_levels;
-    Carver c(workspace);
-    unsigned long long* cutoff = c.take<unsigned long long>(slots);
-    float* cand_iou = c.take<float>(slots * SSDK_ATSS_MAX_TOPK);
     if (total_gt > 0) {
         hipLaunchKernelGGL(atss_candidates_kernel, dim3(total_gt, n_levels), dim3(kAtssThreads), 0, s, gt_rows, gt_stride, gt_offsets, batch,
-                           (const float4*)anchors, lv, topk, cutoff, cand_iou);
+                           (const float4*)anchors, lv, topk, w.cutoff, w.cand_iou);
         SSDK_CHECK_LAUNCH("atss_candidates_kernel");
     }
     dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
     hipLaunchKernelGGL(atss_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors, lv,
-                       topk, cutoff, cand_iou, target, box_idx);
+                       topk, w.cutoff, w.cand_iou, target, box_idx);
     SSDK_CHECK_LAUNCH("atss_assign_kernel");
     return SSDK_OK;
 }
 
-static inline size_t tal_slots(int total_gt) { return (size_t)(total_gt > 0 ? total_gt : 1); }
+struct TalWorkspace { unsigned long long* cutoff; int* cand_anchor; float* cand_m; float* cand_u; int* cand_kept; size_t bytes; };
+// (a box's list has SSDK_TAL_MAX_TOPK slots whatever topk is: the slot of (box, rank) does not move with it)
+static TalWorkspace carve_tal(void* base, int total_gt) {
+    const size_t list = box_slots(total_gt) * SSDK_TAL_MAX_TOPK;
+    Carver c(base);
+    TalWorkspace w;
+    w.cutoff = c.take<unsigned long long>(box_slots(total_gt));
+    w.cand_anchor = c.take<int>(list);
+    w.cand_m = c.take<float>(list);
+    w.cand_u = c.take<float>(list);
+    w.cand_kept = c.take<int>(list);
+    w.bytes = c.off;
+    return w;
+}
 
 extern "C" size_t ssdk_encode_ground_truth_tal_workspace_bytes(int batch, int total_gt, int topk) {
     (void)batch;
-    (void)topk;   // (a box's list has SSDK_TAL_MAX_TOPK slots whatever topk is: the slot of (box, rank) does not move with it)
-    Carver c(nullptr);
-    c.take<unsigned long long>(tal_slots(total_gt));
-    c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    return c.off;
+    (void)topk;
+    return carve_tal(nullptr, total_gt).bytes;
 }
 
 extern "C" int ssdk_encode_ground_truth_tal(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
                                             const float* anchors, int num_anchors, const float* scores, int num_columns, const float* locs,
                                             float xy_scale, float wh_scale, int topk, float alpha, float beta, float* target, int32_t* box_idx,
                                             void* workspace, size_t workspace_bytes, void* stream) {
-    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_tal: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
-    SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: batch exceeds grid limits");
-    SSDK_REQUIRE(gt_offsets && anchors && target && (gt_rows || total_gt == 0), SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: null pointer");
-    SSDK_REQUIRE(scores && locs, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: null scores or locs (the rule reads the anchors' own predictions)");
-    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: gt_stride=%d < 6", gt_stride);
-    SSDK_REQUIRE(num_columns >= 1, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: num_columns=%d < 1", num_columns);
-    SSDK_REQUIRE(topk >= 1 && topk <= SSDK_TAL_MAX_TOPK, SSDK_E_INVALID, "ssdk_encode_ground_truth_tal: topk=%d outside 1..%d", topk,
-                 SSDK_TAL_MAX_TOPK);
+    const char* entry = "ssdk_encode_ground_truth_tal";
+    const TalWorkspace w = carve_tal(workspace, total_gt);
+    int e = check_encode_args(entry, gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, target, kNoFurtherPointers,
+                              kBatchLimitOnly);
+    if (e != SSDK_OK) return e;
+    if ((e = check_prediction_args(entry, anchors, scores, num_columns, locs)) != SSDK_OK) return e;
+    SSDK_REQUIRE(topk >= 1 && topk <= SSDK_TAL_MAX_TOPK, SSDK_E_INVALID, "%s: topk=%d outside 1..%d", entry, topk, SSDK_TAL_MAX_TOPK);
     SSDK_REQUIRE(alpha >= 0.0f && alpha <= FLT_MAX && beta >= 0.0f && beta <= FLT_MAX, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_tal: alpha=%g beta=%g must be finite and not negative", (double)alpha, (double)beta);
-    SSDK_REQUIRE((((uintptr_t)anchors | (uintptr_t)locs) & 15) == 0, SSDK_E_UNSUPPORTED,
-                 "ssdk_encode_ground_truth_tal: anchors and locs must be 16-byte aligned");
-    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_tal_workspace_bytes(batch, total_gt, topk), SSDK_E_WORKSPACE,
-                 "ssdk_encode_ground_truth_tal: workspace too small");
+                 "%s: alpha=%g beta=%g must be finite and not negative", entry, (double)alpha, (double)beta);
+    if ((e = check_workspace(entry, workspace, workspace_bytes, w.bytes)) != SSDK_OK) return e;
     hipStream_t s = (hipStream_t)stream;
-    Carver c(workspace);
-    unsigned long long* cutoff = c.take<unsigned long long>(tal_slots(total_gt));
-    int* cand_anchor = c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    float* cand_m = c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    float* cand_u = c.take<float>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
-    int* cand_kept = c.take<int>(tal_slots(total_gt) * SSDK_TAL_MAX_TOPK);
     TalParams tp;
     tp.xy_scale = xy_scale; tp.wh_scale = wh_scale; tp.alpha = alpha; tp.beta = beta; tp.C = num_columns;
     if (total_gt > 0) {
         hipLaunchKernelGGL(tal_candidates_kernel, dim3(total_gt), dim3(kTalThreads), 0, s, gt_rows, gt_stride, gt_offsets, batch,
-                           (const float4*)anchors, num_anchors, scores, (const float4*)locs, tp, topk, cutoff, cand_anchor, cand_m, cand_u, cand_kept);
+                           (const float4*)anchors, num_anchors, scores, (const float4*)locs, tp, topk, w.cutoff, w.cand_anchor, w.cand_m, w.cand_u,
+                           w.cand_kept);
         SSDK_CHECK_LAUNCH("tal_candidates_kernel");
     }
     dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
     hipLaunchKernelGGL(tal_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors,
-                       scores, (const float4*)locs, tp, cutoff, cand_anchor, cand_kept, target, box_idx);
+                       scores, (const float4*)locs, tp, w.cutoff, w.cand_anchor, w.cand_kept, target, box_idx);
     SSDK_CHECK_LAUNCH("tal_assign_kernel");
     if (total_gt > 0) {
         hipLaunchKernelGGL(tal_normalise_kernel, dim3(cdiv(total_gt, kTalNormThreads / kWave)), dim3(kTalNormThreads), 0, s, gt_rows, gt_stride,
-                           gt_offsets, batch, num_anchors, cand_anchor, cand_m, cand_u, cand_kept, target);
+                           gt_offsets, batch, num_anchors, w.cand_anchor, w.cand_m, w.cand_u, w.cand_kept, target);
         SSDK_CHECK_LAUNCH("tal_normalise_kernel");
     }
     return SSDK_OK;
 }
 
-static inline size_t simota_rows(int batch, int num_anchors) { return (size_t)(batch > 0 ? batch : 1) * (size_t)(num_anchors > 0 ? num_anchors : 1); }
+struct SimotaWorkspace { float* class_sum; unsigned long long* cutoff; size_t bytes; };
+static SimotaWorkspace carve_simota(void* base, int batch, int total_gt, int num_anchors) {
+    Carver c(base);
+    SimotaWorkspace w;
+    w.class_sum = c.take<float>((size_t)(batch > 0 ? batch : 1) * (size_t)(num_anchors > 0 ? num_anchors : 1));   // S_a, written at region anchors only
+    w.cutoff = c.take<unsigned long long>(box_slots(total_gt));                                                   // the boxes' cutoff keys
+    w.bytes = c.off;
+    return w;
+}
 
 extern "C" size_t ssdk_encode_ground_truth_simota_workspace_bytes(int batch, int total_gt, int num_anchors, int n_levels) {
     (void)n_levels;   // (the level table travels by value)
-    Carver c(nullptr);
-    c.take<float>(simota_rows(batch, num_anchors));               // S_a, written at region anchors only
-    c.take<unsigned long long>(tal_slots(total_gt));              // the boxes' cutoff keys
-    return c.off;
+    return carve_simota(nullptr, batch, total_gt, num_anchors).bytes;
 }
 
 extern "C" int ssdk_encode_ground_truth_simota(const float* gt_rows, int gt_stride, const int32_t* gt_offsets, int batch, int total_gt,
@@ -1391,63 +1398,44 @@ extern "C" int ssdk_encode_ground_truth_simota(const float* gt_rows, int gt_stri
                                                int n_levels, const float* scores, int num_columns, const float* locs, float xy_scale,
                                                float wh_scale, float center_radius, int candidate_topk, float iou_weight, float* target,
                                                int32_t* box_idx, int32_t* dynamic_k, void* workspace, size_t workspace_bytes, void* stream) {
-    SSDK_REQUIRE(batch > 0 && num_anchors > 0 && total_gt >= 0, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_simota: batch=%d anchors=%d total_gt=%d", batch, num_anchors, total_gt);
-    SSDK_REQUIRE(batch <= 65535, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: batch exceeds grid limits");
-    SSDK_REQUIRE(gt_offsets && anchors && target && level_sizes && level_strides && (gt_rows || total_gt == 0), SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_simota: null pointer");
-    SSDK_REQUIRE(scores && locs, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: null scores or locs (the rule reads the anchors' own predictions)");
-    SSDK_REQUIRE(gt_stride >= 6, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: gt_stride=%d < 6", gt_stride);
-    SSDK_REQUIRE(num_columns >= 1, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: num_columns=%d < 1", num_columns);
-    SSDK_REQUIRE(n_levels >= 1 && n_levels <= SSDK_ATSS_MAX_LEVELS, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: n_levels=%d outside 1..%d",
-                 n_levels, SSDK_ATSS_MAX_LEVELS);
-    SSDK_REQUIRE(candidate_topk >= 1 && candidate_topk <= SSDK_SIMOTA_MAX_TOPK, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_simota: candidate_topk=%d outside 1..%d", candidate_topk, SSDK_SIMOTA_MAX_TOPK);
-    SSDK_REQUIRE(center_radius > 0.0f && center_radius <= FLT_MAX, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_simota: center_radius=%g must be finite and positive", (double)center_radius);
-    SSDK_REQUIRE(iou_weight >= 0.0f && iou_weight <= FLT_MAX, SSDK_E_INVALID,
-                 "ssdk_encode_ground_truth_simota: iou_weight=%g must be finite and not negative", (double)iou_weight);
-    SimotaLevels lv;
-    lv.n = n_levels;
-    long long sum = 0;
-    for (int l = 0; l <= SSDK_ATSS_MAX_LEVELS; ++l) {
-        lv.off[l] = (int)sum;   // (the entries past n_levels repeat the total)
-        if (l < SSDK_ATSS_MAX_LEVELS) lv.rx[l] = lv.ry[l] = 0.0f;
-        if (l < n_levels) {
-            SSDK_REQUIRE(level_sizes[l] > 0, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: level_sizes[%d]=%d", l, level_sizes[l]);
-            sum += level_sizes[l];
-            SSDK_REQUIRE(sum <= num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: level sizes exceed the %d anchors", num_anchors);
-            const float sx = level_strides[2 * l], sy = level_strides[2 * l + 1];
-            SSDK_REQUIRE(sx > 0.0f && sx <= FLT_MAX && sy > 0.0f && sy <= FLT_MAX, SSDK_E_INVALID,
-                         "ssdk_encode_ground_truth_simota: level_strides[%d]=(%g, %g) must be finite and positive", l, (double)sx, (double)sy);
-            const volatile float rx = center_radius * sx, ry = center_radius * sy;   // rule 2: one fp32 product each
-            lv.rx[l] = rx;
-            lv.ry[l] = ry;
-        }
+    const char* entry = "ssdk_encode_ground_truth_simota";
+    const SimotaWorkspace w = carve_simota(workspace, batch, total_gt, num_anchors);
+    int e = check_encode_args(entry, gt_rows, gt_stride, gt_offsets, batch, total_gt, anchors, num_anchors, target, level_sizes && level_strides,
+                              kBatchLimitOnly);
+    if (e != SSDK_OK) return e;
+    if ((e = check_prediction_args(entry, anchors, scores, num_columns, locs)) != SSDK_OK) return e;
+    SSDK_REQUIRE(candidate_topk >= 1 && candidate_topk <= SSDK_SIMOTA_MAX_TOPK, SSDK_E_INVALID, "%s: candidate_topk=%d outside 1..%d", entry,
+                 candidate_topk, SSDK_SIMOTA_MAX_TOPK);
+    SSDK_REQUIRE(center_radius > 0.0f && center_radius <= FLT_MAX, SSDK_E_INVALID, "%s: center_radius=%g must be finite and positive", entry,
+                 (double)center_radius);
+    SSDK_REQUIRE(iou_weight >= 0.0f && iou_weight <= FLT_MAX, SSDK_E_INVALID, "%s: iou_weight=%g must be finite and not negative", entry,
+                 (double)iou_weight);
+    SimotaLevels lv = {};
+    if ((e = build_levels(entry, level_sizes, n_levels, num_anchors, lv.lv)) != SSDK_OK) return e;
+    for (int l = 0; l < n_levels; ++l) {
+        const float sx = level_strides[2 * l], sy = level_strides[2 * l + 1];
+        SSDK_REQUIRE(sx > 0.0f && sx <= FLT_MAX && sy > 0.0f && sy <= FLT_MAX, SSDK_E_INVALID,
+                     "%s: level_strides[%d]=(%g, %g) must be finite and positive", entry, l, (double)sx, (double)sy);
+        const volatile float rx = center_radius * sx, ry = center_radius * sy;   // rule 2: one fp32 product each
+        lv.rx[l] = rx;
+        lv.ry[l] = ry;
     }
-    SSDK_REQUIRE(sum == num_anchors, SSDK_E_INVALID, "ssdk_encode_ground_truth_simota: level sizes sum to %lld, not to the %d anchors", sum,
-                 num_anchors);
-    SSDK_REQUIRE((((uintptr_t)anchors | (uintptr_t)locs) & 15) == 0, SSDK_E_UNSUPPORTED,
-                 "ssdk_encode_ground_truth_simota: anchors and locs must be 16-byte aligned");
-    SSDK_REQUIRE(workspace && workspace_bytes >= ssdk_encode_ground_truth_simota_workspace_bytes(batch, total_gt, num_anchors, n_levels),
-                 SSDK_E_WORKSPACE, "ssdk_encode_ground_truth_simota: workspace too small");
+    if ((e = check_workspace(entry, workspace, workspace_bytes, w.bytes)) != SSDK_OK) return e;
     hipStream_t s = (hipStream_t)stream;
-    Carver c(workspace);
-    float* class_sum = c.take<float>(simota_rows(batch, num_anchors));
-    unsigned long long* cutoff = c.take<unsigned long long>(tal_slots(total_gt));
     SimotaParams sp;
     sp.xy_scale = xy_scale; sp.wh_scale = wh_scale; sp.iou_weight = iou_weight; sp.C = num_columns;
     dim3 grid(cdiv(num_anchors, kAssignThreads), batch);
     if (total_gt > 0) {
         hipLaunchKernelGGL(simota_class_sum_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors,
-                           num_anchors, lv, scores, num_columns, class_sum);
+                           num_anchors, lv, scores, num_columns, w.class_sum);
         SSDK_CHECK_LAUNCH("simota_class_sum_kernel");
         hipLaunchKernelGGL(simota_candidates_kernel, dim3(total_gt), dim3(kSimotaThreads), 0, s, gt_rows, gt_stride, gt_offsets, batch,
-                           (const float4*)anchors, num_anchors, lv, scores, (const float4*)locs, class_sum, sp, candidate_topk, cutoff, dynamic_k);
+                           (const float4*)anchors, num_anchors, lv, scores, (const float4*)locs, w.class_sum, sp, candidate_topk, w.cutoff,
+                           dynamic_k);
         SSDK_CHECK_LAUNCH("simota_candidates_kernel");
     }
     hipLaunchKernelGGL(simota_assign_kernel, grid, dim3(kAssignThreads), 0, s, gt_rows, gt_stride, gt_offsets, (const float4*)anchors, num_anchors, lv,
-                       scores, (const float4*)locs, class_sum, sp, cutoff, target, box_idx);
+                       scores, (const float4*)locs, w.class_sum, sp, w.cutoff, target, box_idx);
     SSDK_CHECK_LAUNCH("simota_assign_kernel");
     return SSDK_OK;
 }

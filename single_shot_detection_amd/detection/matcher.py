@@ -46,6 +46,16 @@ def match_bipartite(weights, inplace=False):
     return torch.arange(G, dtype=torch.int64, device=w.device), anchor_idx
 
 
+def _gt_rows(gt_boxes, gt_classes=None):
+    """One image's [G, 6] rows for the assigners: the corners; with ``gt_classes`` also the class and a score of 1, else both 0."""
+    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
+    gt[:, :4] = gt_boxes[:, :4]
+    if gt_classes is not None:
+        gt[:, 4] = gt_classes.to(gt.device).reshape(-1).float()
+        gt[:, 5] = 1.0
+    return gt
+
+
 def match_boxes(gt_boxes, anchors, matched_threshold, unmatched_threshold=None, force_match='per_prediction'):
     """box_idx int64 [A] for one image: IoU (box_utils.py:83-101) + match_per_prediction (matcher.py:33-56,
     force_match_for_each_target=True) on the GPU.  ``gt_boxes`` [G, >=4] corner form, ``anchors`` [A,4] centroid.
@@ -53,8 +63,7 @@ def match_boxes(gt_boxes, anchors, matched_threshold, unmatched_threshold=None, 
     from .target_assigner import TargetAssigner
     if unmatched_threshold is None:
         unmatched_threshold = matched_threshold
-    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
-    gt[:, :4] = gt_boxes[:, :4]
+    gt = _gt_rows(gt_boxes)
     _, idx = TargetAssigner(matched_threshold, unmatched_threshold, force_match).encode_ground_truth([gt], anchors, return_box_idx=True)
     return idx[0].long()
 
@@ -64,8 +73,7 @@ def match_atss(gt_boxes, anchors, level_sizes, topk=9):
     anchor is positive for, else NOT_MATCHED -- there is no ignore band and no force stage.  ``gt_boxes`` [G, >=4] corner form,
     ``anchors`` [A,4] centroid, ``level_sizes`` the anchor count of every pyramid level."""
     from .target_assigner import AtssTargetAssigner
-    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
-    gt[:, :4] = gt_boxes[:, :4]
+    gt = _gt_rows(gt_boxes)
     _, idx = AtssTargetAssigner(topk).encode_ground_truth([gt], anchors, return_box_idx=True, level_sizes=level_sizes)
     return idx[0].long()
 
@@ -101,10 +109,7 @@ def match_task_aligned(gt_boxes, gt_classes, anchors, scores, locs, box_coder, t
     (1-based: class k is column k - 1 of the logits), ``anchors`` [A, 4] centroid, ``scores`` [A, C] (or [A * C]) class logits and ``locs``
     [A, 4] (or [A * 4]) encoded boxes of that image, ``box_coder`` the coder that decodes them."""
     from .target_assigner import TaskAlignedAssigner
-    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
-    gt[:, :4] = gt_boxes[:, :4]
-    gt[:, 4] = gt_classes.to(gt.device).reshape(-1).float()
-    gt[:, 5] = 1.0
+    gt = _gt_rows(gt_boxes, gt_classes)
     _, idx = TaskAlignedAssigner(topk, alpha, beta).encode_ground_truth([gt], anchors, (scores.reshape(1, -1), locs.reshape(1, -1)), box_coder,
                                                                          return_box_idx=True)
     return idx[0].long()
@@ -118,10 +123,7 @@ def match_simota(gt_boxes, gt_classes, anchors, scores, locs, box_coder, level_s
     encoded boxes of that image, ``box_coder`` the coder that decodes them, ``level_sizes`` the anchor count and ``level_strides`` the
     ``(sx, sy)`` image pixels per cell of every pyramid level."""
     from .target_assigner import SimOtaAssigner
-    gt = torch.zeros((gt_boxes.size(0), 6), dtype=torch.float32, device=gt_boxes.device)
-    gt[:, :4] = gt_boxes[:, :4]
-    gt[:, 4] = gt_classes.to(gt.device).reshape(-1).float()
-    gt[:, 5] = 1.0
+    gt = _gt_rows(gt_boxes, gt_classes)
     _, idx = SimOtaAssigner(center_radius, candidate_topk, iou_weight).encode_ground_truth(
         [gt], anchors, (scores.reshape(1, -1), locs.reshape(1, -1)), box_coder, level_sizes=level_sizes, level_strides=level_strides,
         return_box_idx=True)

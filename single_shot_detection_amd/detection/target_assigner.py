@@ -85,10 +85,80 @@ def pack_ground_truth(ground_truth, device, row=GT_ROW):
     return rows.contiguous(), offs, total
 
 
+class _Assigner(object):
+    """What the four assigners do around their library call.  Every ``ssdk_encode_ground_truth*`` entry takes (rows, stride, offsets, batch,
+    total, anchors, num_anchors, <its own arguments>, target, box_idx, <its further outputs>, workspace, bytes, stream) and has a
+    ``*_workspace_bytes(batch, total, ...)`` beside it."""
+
+    def __init__(self):
+        self._ws = None
+        self._levels = {}
+
+    @staticmethod
+    def _pack(ground_truth, device):
+        """(rows, offsets, total) of a list of per-image tensors or of a ``PackedGroundTruth``."""
+        if isinstance(ground_truth, PackedGroundTruth):
+            return ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
+        return pack_ground_truth(ground_truth, device)
+
+    def _encode(self, entry, ground_truth, anchors, return_box_idx, ws_args, args, outputs=(), keep=(), packed=None):
+        """Packs the ground truth, allocates ``target`` / ``box_idx``, grows the workspace and calls ``entry``: (target, box_idx)."""
+        lib = _lib.lib()
+        device = anchors.device
+        batch_size = len(ground_truth)
+        num_anchors = anchors.size(0)
+        anchors = anchors.contiguous().float()
+        rows, offs, total = packed or self._pack(ground_truth, device)
+        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
+        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
+        need = getattr(lib, entry + '_workspace_bytes')(batch_size, total, *ws_args)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
+        _lib.check(getattr(lib, entry)(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors, *args,
+                                       _lib.ptr(target), _lib.ptr(box_idx), *outputs, _lib.ptr(self._ws), self._ws.numel(),
+                                       _lib.current_stream()), entry)
+        # keep the staging tensors alive until the stream has consumed them
+        target._ssdk_keepalive = (rows, offs) + tuple(keep)
+        return target, box_idx
+
+    def _prediction(self, prediction, box_coder):
+        """``prediction = (scores, locs)`` and the box coder are there: (scores, locs)."""
+        name = type(self).__name__
+        if prediction is None or len(prediction) != 2:
+            raise ValueError(f'{name}.encode_ground_truth: prediction must be (scores, locs)')
+        if box_coder is None:
+            raise ValueError(f'{name}.encode_ground_truth: box_coder is required (its scales decode the predicted boxes)')
+        return prediction
+
+    def _prepare(self, scores, locs, box_coder, batch_size, num_anchors):
+        """The predictions as the library reads them -- detached, integrated where the coder is integral, fp32, contiguous -- and their
+        shapes checked: (scores, locs, num_columns)."""
+        name = type(self).__name__
+        with torch.no_grad():
+            scores, locs = scores.detach(), locs.detach()
+            if hasattr(box_coder, 'integrate'):
+                locs = box_coder.integrate(locs, num_anchors)
+            scores, locs = scores.float().contiguous(), locs.float().contiguous()
+        if scores.shape[0] != batch_size or locs.shape[0] != batch_size or locs.numel() != batch_size * num_anchors * 4:
+            raise ValueError(f'{name}.encode_ground_truth: locs of shape {tuple(locs.shape)} / scores of shape '
+                             f'{tuple(scores.shape)} for a batch of {batch_size} and {num_anchors} anchors')
+        num_columns, rest = divmod(scores.numel(), batch_size * num_anchors)
+        if rest or num_columns < 1:
+            raise ValueError(f'{name}.encode_ground_truth: scores of shape {tuple(scores.shape)} are not [Batch, {num_anchors} * C]')
+        return scores, locs, num_columns
+
+    def _level_table(self, sizes, strides=()):
+        """The host arrays the library reads the levels from, built once per (sizes, strides): (int32 sizes, float (sx, sy) pairs)."""
+        key = (sizes, strides)
+        if key not in self._levels:
+            self._levels[key] = ((ctypes.c_int32 * len(sizes))(*sizes), (ctypes.c_float * (2 * len(strides)))(*[v for s in strides for v in s]))
+        return self._levels[key]
+
+
 FORCE_MATCH = {'per_prediction': 0, 'bipartite': 1}   # SSDK_FORCE_MATCH_* (include/ssdk.h)
 
 
-class TargetAssigner(object):
+class TargetAssigner(_Assigner):
     """``force_match`` (not in the reference; default ``'per_prediction'`` = the reference's rule): how every ground-truth box is given
     an anchor regardless of the thresholds.  ``'per_prediction'``: each box's best anchor, the highest box index winning an anchor that
     several boxes share (matcher.py:52-54) -- the boxes that lose it may end up with no positive anchor at all.  ``'bipartite'``: the
@@ -99,10 +169,10 @@ class TargetAssigner(object):
     def __init__(self, matched_threshold, unmatched_threshold, force_match='per_prediction'):
         if force_match not in FORCE_MATCH:
             raise ValueError(f'TargetAssigner: force_match={force_match!r}, expected one of {sorted(FORCE_MATCH)}')
+        super().__init__()
         self.matched_threshold = matched_threshold
         self.unmatched_threshold = unmatched_threshold
         self.force_match = force_match
-        self._ws = None
 
     def encode_ground_truth(self, ground_truth, anchors, return_box_idx=False):
         """
@@ -115,43 +185,19 @@ class TargetAssigner(object):
             and so is the result -- the ``target.to(device)`` of detection/init.py:115 becomes a no-op)
         """
         _lib.require_cuda(anchors)
-        lib = _lib.lib()
-        device = anchors.device
-        batch_size = len(ground_truth)
-        num_anchors = anchors.size(0)
-        anchors = anchors.contiguous().float()
-        if isinstance(ground_truth, PackedGroundTruth):
-            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
-        else:
-            rows, offs, total = pack_ground_truth(ground_truth, device)
-        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
-        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
         mode = FORCE_MATCH[self.force_match]
-        need = lib.ssdk_encode_ground_truth_ex_workspace_bytes(batch_size, total, mode) if mode else \
-            lib.ssdk_encode_ground_truth_workspace_bytes(batch_size, total)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
+        thresholds = (float(self.matched_threshold), float(self.unmatched_threshold))
         if mode:
-            _lib.check(lib.ssdk_encode_ground_truth_ex(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total,
-                                                       _lib.ptr(anchors), num_anchors, float(self.matched_threshold),
-                                                       float(self.unmatched_threshold), mode, _lib.ptr(target), _lib.ptr(box_idx),
-                                                       _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
-                       'ssdk_encode_ground_truth_ex')
+            target, box_idx = self._encode('ssdk_encode_ground_truth_ex', ground_truth, anchors, return_box_idx, (mode,), thresholds + (mode,))
         else:   # the default: the entry point and the kernels it always had
-            _lib.check(lib.ssdk_encode_ground_truth(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total,
-                                                    _lib.ptr(anchors), num_anchors, float(self.matched_threshold),
-                                                    float(self.unmatched_threshold), _lib.ptr(target), _lib.ptr(box_idx),
-                                                    _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
-                       'ssdk_encode_ground_truth')
-        # keep the staging tensors alive until the stream has consumed them
-        target._ssdk_keepalive = (rows, offs)
+            target, box_idx = self._encode('ssdk_encode_ground_truth', ground_truth, anchors, return_box_idx, (), thresholds)
         return (target, box_idx) if return_box_idx else target
 
 
 ATSS_MAX_TOPK = 32     # SSDK_ATSS_MAX_TOPK (include/ssdk.h)
 
 
-class AtssTargetAssigner(object):
+class AtssTargetAssigner(_Assigner):
     """Adaptive Training Sample Selection (arXiv:1912.02424, Algorithm 1; not in the reference) in place of the two IoU thresholds.  Per
     ground-truth box the ``topk`` anchors of every pyramid level nearest to the box centre are its candidates; the mean plus the
     (unbiased) standard deviation of their IoUs is that box's own threshold; a candidate is positive when its IoU reaches the threshold
@@ -162,9 +208,8 @@ class AtssTargetAssigner(object):
     def __init__(self, topk=9):
         if int(topk) != topk or not 1 <= topk <= ATSS_MAX_TOPK:
             raise ValueError(f'AtssTargetAssigner: topk={topk!r}, expected an integer in 1..{ATSS_MAX_TOPK}')
+        super().__init__()
         self.topk = int(topk)
-        self._ws = None
-        self._levels = {}
 
     def encode_ground_truth(self, ground_truth, anchors, return_box_idx=False, level_sizes=None):
         """Inputs and outputs as ``TargetAssigner.encode_ground_truth``; ``level_sizes``: the anchor count of every pyramid level, in the
@@ -176,34 +221,16 @@ class AtssTargetAssigner(object):
         if sum(sizes) != num_anchors:
             raise ValueError(f'AtssTargetAssigner.encode_ground_truth: level_sizes sum to {sum(sizes)}, the anchors are {num_anchors}')
         _lib.require_cuda(anchors)
-        if sizes not in self._levels:
-            self._levels[sizes] = (ctypes.c_int32 * len(sizes))(*sizes)
-        lib = _lib.lib()
-        device = anchors.device
-        batch_size = len(ground_truth)
-        anchors = anchors.contiguous().float()
-        if isinstance(ground_truth, PackedGroundTruth):
-            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
-        else:
-            rows, offs, total = pack_ground_truth(ground_truth, device)
-        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
-        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
-        need = lib.ssdk_encode_ground_truth_atss_workspace_bytes(batch_size, total, len(sizes))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
-        _lib.check(lib.ssdk_encode_ground_truth_atss(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors,
-                                                     self._levels[sizes], len(sizes), self.topk, _lib.ptr(target), _lib.ptr(box_idx),
-                                                     _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
-                   'ssdk_encode_ground_truth_atss')
-        # keep the staging tensors alive until the stream has consumed them
-        target._ssdk_keepalive = (rows, offs)
+        c_sizes, _ = self._level_table(sizes)
+        target, box_idx = self._encode('ssdk_encode_ground_truth_atss', ground_truth, anchors, return_box_idx, (len(sizes),),
+                                       (c_sizes, len(sizes), self.topk))
         return (target, box_idx) if return_box_idx else target
 
 
 TAL_MAX_TOPK = 32      # SSDK_TAL_MAX_TOPK (include/ssdk.h)
 
 
-class TaskAlignedAssigner(object):
+class TaskAlignedAssigner(_Assigner):
     """Task Alignment Learning (TOOD, arXiv:2108.07755 section 3.2; not in the reference): the prediction-aware assigner of TOOD,
     PP-YOLOE and YOLOv6/v8.  An anchor is a candidate of a box when its centre lies strictly inside the box and its alignment
     ``m = s^alpha * u^beta`` -- ``s`` its OWN predicted probability of the box's class (sigmoid layout: class k is column k - 1), ``u``
@@ -223,52 +250,20 @@ class TaskAlignedAssigner(object):
                 ok = False
             if not ok:
                 raise ValueError(f'TaskAlignedAssigner: {name}={v!r}, expected a finite number >= 0')
+        super().__init__()
         self.topk, self.alpha, self.beta = int(topk), float(alpha), float(beta)
-        self._ws = None
 
     def encode_ground_truth(self, ground_truth, anchors, prediction, box_coder, return_box_idx=False):
         """Inputs and outputs as ``TargetAssigner.encode_ground_truth``; beside them ``prediction = (scores, locs)`` as the detector returns
         them (``[Batch, AnchorBoxes * C]`` class logits -- C is taken from the shape -- and ``[Batch, AnchorBoxes * 4]`` encoded boxes) and
         the ``box_coder`` whose ``xy_scale`` / ``wh_scale`` decode them.  With an ``IntegralBoxCoder`` the loc head's distributions are
         first integrated (``box_coder.integrate`` under ``no_grad``): one more pass over the loc logits than the loss itself makes."""
-        if prediction is None or len(prediction) != 2:
-            raise ValueError('TaskAlignedAssigner.encode_ground_truth: prediction must be (scores, locs)')
-        if box_coder is None:
-            raise ValueError('TaskAlignedAssigner.encode_ground_truth: box_coder is required (its scales decode the predicted boxes)')
-        scores, locs = prediction
+        scores, locs = self._prediction(prediction, box_coder)
         _lib.require_cuda(anchors, scores, locs)
-        lib = _lib.lib()
-        device = anchors.device
-        batch_size = len(ground_truth)
-        num_anchors = anchors.size(0)
-        anchors = anchors.contiguous().float()
-        with torch.no_grad():
-            scores, locs = scores.detach(), locs.detach()
-            if hasattr(box_coder, 'integrate'):
-                locs = box_coder.integrate(locs, num_anchors)
-            scores, locs = scores.float().contiguous(), locs.float().contiguous()
-        if scores.shape[0] != batch_size or locs.shape[0] != batch_size or locs.numel() != batch_size * num_anchors * 4:
-            raise ValueError(f'TaskAlignedAssigner.encode_ground_truth: locs of shape {tuple(locs.shape)} / scores of shape '
-                             f'{tuple(scores.shape)} for a batch of {batch_size} and {num_anchors} anchors')
-        num_columns, rest = divmod(scores.numel(), batch_size * num_anchors)
-        if rest or num_columns < 1:
-            raise ValueError(f'TaskAlignedAssigner.encode_ground_truth: scores of shape {tuple(scores.shape)} are not [Batch, {num_anchors} * C]')
-        if isinstance(ground_truth, PackedGroundTruth):
-            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
-        else:
-            rows, offs, total = pack_ground_truth(ground_truth, device)
-        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
-        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
-        need = lib.ssdk_encode_ground_truth_tal_workspace_bytes(batch_size, total, self.topk)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
-        _lib.check(lib.ssdk_encode_ground_truth_tal(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors,
-                                                    _lib.ptr(scores), num_columns, _lib.ptr(locs), float(box_coder.xy_scale),
-                                                    float(box_coder.wh_scale), self.topk, self.alpha, self.beta, _lib.ptr(target),
-                                                    _lib.ptr(box_idx), _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
-                   'ssdk_encode_ground_truth_tal')
-        # keep the staging tensors alive until the stream has consumed them
-        target._ssdk_keepalive = (rows, offs, scores, locs)
+        scores, locs, num_columns = self._prepare(scores, locs, box_coder, len(ground_truth), anchors.size(0))
+        target, box_idx = self._encode('ssdk_encode_ground_truth_tal', ground_truth, anchors, return_box_idx, (self.topk,),
+                                       (_lib.ptr(scores), num_columns, _lib.ptr(locs), float(box_coder.xy_scale), float(box_coder.wh_scale),
+                                        self.topk, self.alpha, self.beta), keep=(scores, locs))
         return (target, box_idx) if return_box_idx else target
 
 
@@ -276,7 +271,7 @@ SIMOTA_MAX_TOPK = 32   # SSDK_SIMOTA_MAX_TOPK (include/ssdk.h)
 SIMOTA_MAX_LEVELS = 16   # SSDK_ATSS_MAX_LEVELS
 
 
-class SimOtaAssigner(object):
+class SimOtaAssigner(_Assigner):
     """SimOTA (YOLOX, arXiv:2107.08430 section 2.4: OTA with the Sinkhorn iteration replaced by a dynamic top-k; not in the reference):
     the assigner that decides HOW MANY positives a box gets from the prediction itself.  A box's region is the anchors whose centre lies
     strictly inside it or inside a square of ``center_radius`` cells of the anchor's own level around the box centre; the cost of a region
@@ -303,9 +298,8 @@ class SimOtaAssigner(object):
                 ok = False
             if not ok:
                 raise ValueError(f"SimOtaAssigner: {name}={v!r}, expected a finite number {'> 0' if strict else '>= 0'}")
+        super().__init__()
         self.center_radius, self.candidate_topk, self.iou_weight = float(center_radius), int(candidate_topk), float(iou_weight)
-        self._ws = None
-        self._levels = {}
 
     def encode_ground_truth(self, ground_truth, anchors, prediction, box_coder, level_sizes=None, level_strides=None, return_box_idx=False,
                             return_dynamic_k=False):
@@ -315,10 +309,7 @@ class SimOtaAssigner(object):
         ``[capacity]`` tensor of every box's ``k`` (after ``box_idx`` when both are asked for).  With an ``IntegralBoxCoder`` the loc head's
         distributions are first integrated (``box_coder.integrate`` under ``no_grad``): one more pass over the loc logits than the loss
         itself makes."""
-        if prediction is None or len(prediction) != 2:
-            raise ValueError('SimOtaAssigner.encode_ground_truth: prediction must be (scores, locs)')
-        if box_coder is None:
-            raise ValueError('SimOtaAssigner.encode_ground_truth: box_coder is required (its scales decode the predicted boxes)')
+        scores, locs = self._prediction(prediction, box_coder)
         num_anchors = anchors.size(0)
         if level_sizes is None or level_strides is None:
             raise ValueError('SimOtaAssigner.encode_ground_truth: level_sizes and level_strides are required '
@@ -331,45 +322,15 @@ class SimOtaAssigner(object):
             raise ValueError(f'SimOtaAssigner.encode_ground_truth: {len(strides)} level_strides for {len(sizes)} levels (1..{SIMOTA_MAX_LEVELS})')
         if not all(0.0 < v < float('inf') for s in strides for v in s):
             raise ValueError(f'SimOtaAssigner.encode_ground_truth: level_strides={strides!r} must be finite and positive')
-        scores, locs = prediction
         _lib.require_cuda(anchors, scores, locs)
-        key = (sizes, strides)
-        if key not in self._levels:
-            self._levels[key] = ((ctypes.c_int32 * len(sizes))(*sizes), (ctypes.c_float * (2 * len(sizes)))(*[v for s in strides for v in s]))
-        c_sizes, c_strides = self._levels[key]
-        lib = _lib.lib()
-        device = anchors.device
-        batch_size = len(ground_truth)
-        anchors = anchors.contiguous().float()
-        with torch.no_grad():
-            scores, locs = scores.detach(), locs.detach()
-            if hasattr(box_coder, 'integrate'):
-                locs = box_coder.integrate(locs, num_anchors)
-            scores, locs = scores.float().contiguous(), locs.float().contiguous()
-        if scores.shape[0] != batch_size or locs.shape[0] != batch_size or locs.numel() != batch_size * num_anchors * 4:
-            raise ValueError(f'SimOtaAssigner.encode_ground_truth: locs of shape {tuple(locs.shape)} / scores of shape '
-                             f'{tuple(scores.shape)} for a batch of {batch_size} and {num_anchors} anchors')
-        num_columns, rest = divmod(scores.numel(), batch_size * num_anchors)
-        if rest or num_columns < 1:
-            raise ValueError(f'SimOtaAssigner.encode_ground_truth: scores of shape {tuple(scores.shape)} are not [Batch, {num_anchors} * C]')
-        if isinstance(ground_truth, PackedGroundTruth):
-            rows, offs, total = ground_truth.rows, ground_truth.offsets, ground_truth.rows.shape[0]   # (total = capacity: padding is skipped on the device)
-        else:
-            rows, offs, total = pack_ground_truth(ground_truth, device)
-        target = torch.empty((batch_size, num_anchors, TARGET_SIZE), dtype=torch.float32, device=device)
-        box_idx = torch.empty((batch_size, num_anchors), dtype=torch.int32, device=device) if return_box_idx else None
-        dynamic_k = torch.empty((max(total, 1),), dtype=torch.int32, device=device)[:total] if return_dynamic_k else None
-        need = lib.ssdk_encode_ground_truth_simota_workspace_bytes(batch_size, total, num_anchors, len(sizes))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty((max(need, 4096),), dtype=torch.uint8, device=device)
-        _lib.check(lib.ssdk_encode_ground_truth_simota(_lib.ptr(rows), GT_ROW, _lib.ptr(offs), batch_size, total, _lib.ptr(anchors), num_anchors,
-                                                       c_sizes, c_strides, len(sizes), _lib.ptr(scores), num_columns, _lib.ptr(locs),
-                                                       float(box_coder.xy_scale), float(box_coder.wh_scale), self.center_radius,
-                                                       self.candidate_topk, self.iou_weight, _lib.ptr(target), _lib.ptr(box_idx),
-                                                       _lib.ptr(dynamic_k) if total else None, _lib.ptr(self._ws), self._ws.numel(),
-                                                       _lib.current_stream()),
-                   'ssdk_encode_ground_truth_simota')
-        # keep the staging tensors alive until the stream has consumed them
-        target._ssdk_keepalive = (rows, offs, scores, locs)
+        c_sizes, c_strides = self._level_table(sizes, strides)
+        scores, locs, num_columns = self._prepare(scores, locs, box_coder, len(ground_truth), num_anchors)
+        packed = self._pack(ground_truth, anchors.device)
+        total = packed[2]
+        dynamic_k = torch.empty((max(total, 1),), dtype=torch.int32, device=anchors.device)[:total] if return_dynamic_k else None
+        target, box_idx = self._encode('ssdk_encode_ground_truth_simota', ground_truth, anchors, return_box_idx, (num_anchors, len(sizes)),
+                                       (c_sizes, c_strides, len(sizes), _lib.ptr(scores), num_columns, _lib.ptr(locs), float(box_coder.xy_scale),
+                                        float(box_coder.wh_scale), self.center_radius, self.candidate_topk, self.iou_weight),
+                                       outputs=(_lib.ptr(dynamic_k) if total else None,), keep=(scores, locs), packed=packed)
         out = (target,) + ((box_idx,) if return_box_idx else ()) + ((dynamic_k,) if return_dynamic_k else ())
         return out if len(out) > 1 else target

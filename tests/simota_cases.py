@@ -325,3 +325,26 @@ def generated(name):
     fig = margins(gt, anchors, scores.reshape(len(gt), len(anchors), -1), locs.reshape(len(gt), len(anchors), 4), sizes, strides, **kw)
     assert_margins(fig)
     return gt, anchors, scores, locs, sizes, strides, kw, fig
+
+
+@functools.lru_cache(maxsize=None)
+def one_thread_owns_three_candidates():
+    """``tal_cases.three_anchors_of_one_thread`` for SimOTA: the first box's three largest-u anchors AND its three cheapest are 5, 1 029 and
+    2 053, which one sweep thread owns, so in both pop loops that thread's third key comes from the re-read of its anchors.  Both keys
+    decide the result: with candidate_topk = 7 the sum of the box's largest u is 5.05 with anchor 2 053's u (0.86) in it and 4.71 with the
+    next u in its place, so k_g is 5 or 4; and 2 053 is among the k_g cheapest.  Same tuple as ``generated``; the congruence, the count,
+    what a lost third u does to it and the margins are asserted here, on the CPU."""
+    gt, anchors, scores, locs = tc.three_anchors_of_one_thread(4, 43, (-2.0, 3.0, -2.0, -2.0), shrink=2)
+    sizes, strides, kw = (2500, 3), (16.0, 32.0), dict(candidate_topk=7)
+    rx, ry = level_radii_np(sizes, strides, 2.5)
+    ins, pen, cost, u = box_costs_np(gt[0][0], anchors, scores[0], locs[0], class_sum_np(scores[0]), rx, ry)
+    by_u = np.argsort(-u.astype(np.float64), kind='stable')[:3]
+    by_cost = ins[ranked(ins, pen, cost)[:3]]
+    assert sorted(ins[by_u].tolist()) == [5, 1029, 2053] and sorted(by_cost.tolist()) == [5, 1029, 2053]
+    assert len(set(ins[by_u] % tc.SWEEP_THREADS)) == 1 and len(set(by_cost % tc.SWEEP_THREADS)) == 1
+    fig = margins(gt, anchors, scores, locs, sizes, strides, **kw)
+    assert_margins(fig)
+    k_g = int(fig['k64'][0][0])
+    k_without = dynamic_k_np(np.delete(u, by_u[2]), kw['candidate_topk'])[0]     # the owner's re-read finds nothing: the next u is popped
+    assert k_g >= 3 and k_without != k_g, (k_g, k_without)
+    return gt, anchors, scores.reshape(1, -1), locs.reshape(1, -1), sizes, strides, kw, fig

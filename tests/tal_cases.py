@@ -318,3 +318,38 @@ def generated(name):
     fig = margins(gt, anchors, scores.reshape(len(gt), len(anchors), -1), locs.reshape(len(gt), len(anchors), 4), **kw)
     assert_margins(fig)
     return gt, anchors, scores, locs, kw, fig
+
+
+SWEEP_THREADS = 1024     # kTalThreads / kSimotaThreads: a sweep thread owns the anchors congruent to it mod 1 024
+
+
+def three_anchors_of_one_thread(C, seed, logit, shrink=4):
+    """(gt list of one image, anchors [2 503, 4], scores [1, A, C], locs [1, A, 4]): random anchors and predictions, except that anchors 5,
+    1 029 and 2 053 -- 1 024 apart, so ONE sweep thread owns all three -- sit on the first box, predict themselves (loc 0: u = 1, then
+    smaller by ``shrink`` pixels a side each: about 0.86 and 0.73 at 4) and carry ``logit`` for the box's class.  On the model of ``atss_cases.one_thread_owns_three_candidates``."""
+    rng = np.random.default_rng(seed)
+    n = 2503
+    anchors = np.concatenate([rng.uniform(0, 300, (n, 2)), rng.uniform(20, 120, (n, 2))], axis=1).astype(F)
+    gt = [np.array([_box(100, 100, 160, 150, 2), _box(30, 200, 90, 260, 3)], F)]
+    scores, locs = make_prediction(1, n, C, seed + 1)
+    scores, locs = scores.reshape(1, n, C), locs.reshape(1, n, 4)
+    for j, a in enumerate((5, 1029, 2053)):
+        anchors[a] = (130 + j, 125 - j, 60 - shrink * j, 50 - shrink * j)
+        locs[0, a] = 0
+        scores[0, a] = logit
+    return gt, anchors, scores, locs
+
+
+@functools.lru_cache(maxsize=None)
+def one_thread_owns_three_candidates():
+    """The first box's three best anchors are 5, 1 029 and 2 053: the sweep thread that owns them keeps two keys in registers and finds the
+    third only by re-reading its anchors, and with topk = 4 that key is popped and the box's cutoff lies behind it.  Same tuple as
+    ``generated``; the congruence and the margins are asserted here, on the CPU."""
+    gt, anchors, scores, locs = three_anchors_of_one_thread(4, 41, (-2.0, 3.0, -2.0, -2.0))
+    kw = dict(topk=4)
+    ins, m, _ = box_metrics_np(gt[0][0], anchors, scores[0], locs[0], XY_SCALE, WH_SCALE, 1.0, 6.0)
+    best = ins[_ranked(ins, m)[:3]]
+    assert best.tolist() == [5, 1029, 2053] and len(set(best % SWEEP_THREADS)) == 1 and len(ins) > kw['topk']
+    fig = margins(gt, anchors, scores, locs, **kw)
+    assert_margins(fig)
+    return gt, anchors, scores.reshape(1, -1), locs.reshape(1, -1), kw, fig

@@ -295,3 +295,11 @@ def test_abi_revision_and_limits():
     assert int(re.search(r'#define\s+SSDK_VERSION\s+(\d+)', text).group(1)) >= 132
     assert int(re.search(r'#define\s+SSDK_SIMOTA_MAX_TOPK\s+(\d+)', text).group(1)) == 32
     assert _lib.lib().ssdk_version() >= 132
+
+
+def test_one_thread_owns_three_candidates_case():
+    """The case asserts its own conditions (three largest-u and three cheapest anchors congruent mod 1 024, k_g >= 3, the margins); all
+    three are the first box's positives."""
+    gt, anchors, scores, locs, sizes, strides, kw, fig = sc.one_thread_owns_three_candidates()
+    assert fig['k64'][0][0] >= 3 and sum(sizes) == len(anchors)
+    assert (fig['idx64'][0, [5, 1029, 2053]] == 0).all()

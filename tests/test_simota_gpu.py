@@ -104,6 +104,16 @@ def test_generated_cases_equal_the_restatement(name):
     assert torch.equal(idx, idx5) and torch.equal(k, k5) and np.array_equal(bits(t), bits(t5))
 
 
+def test_one_thread_owns_three_candidates():
+    """The sweep thread that owns the first box's three largest-u and three cheapest anchors finds the third of each by re-reading its
+    anchors (two keys of each kind stay in registers)."""
+    gt, anchors_np, scores_np, locs_np, sizes, strides, kw, fig = sc.one_thread_owns_three_candidates()
+    anchors, scores, locs = (torch.from_numpy(x).cuda() for x in (anchors_np, scores_np, locs_np))
+    t, idx, k = encode(gt, anchors, scores, locs, sizes, strides, kw)
+    assert (fig['idx64'][0, [5, 1029, 2053]] == 0).all() and fig['k64'][0][0] >= 3
+    check('one_thread_owns_three_candidates', t, idx, k, gt, fig['idx64'], fig['k64'])
+
+
 def test_match_simota_is_row_0_of_the_batch_form():
     gt, anchors_np, scores_np, locs_np, sizes, strides, kw, fig = sc.generated('mb2_g32')
     anchors = torch.from_numpy(anchors_np).cuda()

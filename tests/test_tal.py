@@ -216,3 +216,10 @@ def test_config_name_selects_the_assigner():
     with pytest.raises(ValueError):
         det_init.build_target_assigner({'name': 'TaskAlignedAssigner', 'topk': 40})
     assert callable(matcher.match_task_aligned)
+
+
+def test_one_thread_owns_three_candidates_case():
+    """The case asserts its own conditions (three best anchors congruent mod 1 024, the margins); all three are the first box's positives."""
+    gt, anchors, scores, locs, kw, fig = tc.one_thread_owns_three_candidates()
+    assert kw['topk'] >= 3 and len(anchors) > 2 * tc.SWEEP_THREADS + 5
+    assert (fig['idx64'][0, [5, 1029, 2053]] == 0).all()

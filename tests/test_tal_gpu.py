@@ -89,6 +89,15 @@ def test_generated_cases_equal_the_restatement(name):
     assert np.array_equal(bits(t), bits(t4))
 
 
+def test_one_thread_owns_three_candidates():
+    """The sweep thread that owns the first box's three best anchors finds the third by re-reading its anchors (two keys stay in registers)."""
+    gt, anchors_np, scores_np, locs_np, kw, fig = tc.one_thread_owns_three_candidates()
+    anchors, scores, locs = (torch.from_numpy(x).cuda() for x in (anchors_np, scores_np, locs_np))
+    t, idx = encode(gt, anchors, scores, locs, kw)
+    assert (fig['idx64'][0, [5, 1029, 2053]] == 0).all()
+    check('one_thread_owns_three_candidates', t, idx, gt, fig['idx64'], fig['col64'], fig['col5_dev'])
+
+
 def test_match_task_aligned_is_row_0_of_the_batch_form():
     gt, anchors_np, scores_np, locs_np, kw, fig = tc.generated('mb2_g32')
     anchors = torch.from_numpy(anchors_np).cuda()
